@@ -14,9 +14,17 @@ round 1's independent-noise set.
 Before the timed region every engine slot has captured its frame graph (`prime`, independent of
 --warmup), so the steady state does not depend on --steps / --warmup.
 
-N = 1 also reports, in "secondary", the same line for 720p and 4K depth, the stress frames, the
-C2 frame with a host-resident depth map (pinned, H2D overlapped: `value_h2d`), and C3 (720p +
-256-sequence rollbuffer window, tools/bench_c3.py) - each with the roofline of its dominant kernel.
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, primes, warms up, times the K steps and
+prints the line.  `--dump-outputs DIR` also writes what the last timed step left for its caller
+(dump_outputs) as DIR/<name>.npy; the frames and the step order depend on the arguments only, so
+two builds can be compared array for array.
+
+`--full` adds everything else: the byte model and the per-kernel `roofline` (an event-timed pass
+of its own), the CPU baseline (`cpu_baseline`), and at N = 1, in "secondary", the same line for
+720p and 4K depth, the stress frames, the C2 frame with a host-resident depth map (pinned, H2D
+overlapped: `value_h2d`), and C3 (720p + 256-sequence rollbuffer window, tools/bench_c3.py) -
+each with the roofline of its dominant kernel.  `--no-kernel-timing`, `--no-cpu-baseline` and
+`--no-secondary` take single parts out of a `--full` run.
 
 N > 1 (torchrun, one rank per GPU over RCCL): rank k owns camera k (weak scaling).  The shared
 voxel grid needs one real exchange per frame: the per-rank occupancy marks (1 bit per cell) are
@@ -78,7 +86,19 @@ def parse():
     ap.add_argument("--publish", action="store_true",
                     help="fused mode: gather the fused voxel cloud to rank 0 every step (the "
                          "component publishes it every frame)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline line: the byte model and per-kernel roofline "
+                         "(event-timed pass), the CPU baseline and, at N = 1, the secondary "
+                         "configurations (each can be switched off with its --no-... option); "
+                         "without --full a run only sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: after the timed steps, write what the last timed step left "
+                         "for its caller (points, voxel coords, voxelized points, occupancy "
+                         "grids, the batch's frame ranges) as DIR/<name>.npy, float32, at most "
+                         "64 MB in all (a fixed seeded sample of rows where an array is larger "
+                         "than its share)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU leg")
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="per CPU run (5 runs)")
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="do not bracket launches with HIP events (for rocprofv3 runs)")
@@ -322,14 +342,67 @@ def settle(eng, run_some, seconds=SETTLE_S):
     eng.synchronize()
 
 
-def time_single(st, params, steps, warmup, depth, kernel_timing, pmc_key, batch=1):
+DUMP_BYTES = 60 * 1000 * 1000  # of the 64 MB a dump may take (the .npy headers are the rest)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(eng, batch, out_dir):
+    """What the engine's last step left for its caller, as out_dir/<name>.npy: the batch's
+    points and voxel coords (point_ranges: frame j's rows), the voxelized points (voxel_ranges),
+    the occupancy grid after the last frame and the grids after the batch's earlier frames.
+    float32 (float64 where a value does not fit float32's 24 bits).  An array larger than its
+    share of DUMP_BYTES is cut to a sample of its rows: indices drawn once from DUMP_SEED,
+    ascending, the same for the same shape.  Returns {name: {"shape", "rows_saved"}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    _, ncells = eng.grid_size()
+    wide = np.float64 if ncells > (1 << 24) else np.float32
+    arrays = {"points": eng.downloadPoints(), "voxel_coords": eng.downloadVoxelCoords(),
+              "voxelized_points": eng.downloadVoxelizedPoints(),
+              "occupancy_grid": eng.downloadVoxelOccupancyGrid()}
+    small = {}
+    if batch > 1:
+        ps, vs = eng.batch_ranges()
+        arrays["point_ranges"], arrays["voxel_ranges"] = ps, vs
+        # the grids after frames 0 .. batch-2, one row per cell: a fixed small share
+        small["occupancy_grid_batch"] = np.stack(
+            [eng.downloadBatchVoxelOccupancyGrid(j) for j in range(batch - 1)], axis=1)
+    dtype = {"voxel_coords": wide, "point_ranges": np.float64, "voxel_ranges": np.float64}
+
+    def nbytes(name, a):
+        return a.size * np.dtype(dtype.get(name, np.float32)).itemsize
+
+    # shares: the small arrays 4 MB each at most; the others whole while they fit an equal share
+    # of what is left, the larger ones an equal share each
+    share = {k: min(nbytes(k, a), DUMP_BYTES // 15) for k, a in small.items()}
+    left = DUMP_BYTES - sum(share.values())
+    todo = sorted(arrays, key=lambda k: nbytes(k, arrays[k]))
+    for i, k in enumerate(todo):
+        share[k] = min(nbytes(k, arrays[k]), left // (len(todo) - i))
+        left -= share[k]
+    arrays.update(small)
+    info = {}
+    for k, a in arrays.items():
+        rows = a.shape[0]
+        keep = rows if nbytes(k, a) <= share[k] else int(share[k] // max(nbytes(k, a) // rows, 1))
+        if keep < rows:
+            sel = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+            a = a[sel]
+        np.save(os.path.join(out_dir, k + ".npy"), a.astype(dtype.get(k, np.float32)))
+        info[k] = {"shape": list(arrays[k].shape), "rows_saved": keep}
+    return info
+
+
+def time_single(st, params, steps, warmup, depth, kernel_timing, pmc_key, batch=1, full=True,
+                dump_dir=None):
     """Steady-state single-GPU line of one DepthStream: prime (every slot's graph captured),
-    warm-up, K timed steps (a step = one batch of `batch` frames), then the event-timed pass for
-    the roofline."""
+    warm-up, K timed steps (a step = one batch of `batch` frames), the outputs of the last timed
+    step written to dump_dir if given; then, full only, the byte model (two synchronous passes
+    for the counts) and the event-timed pass for the roofline."""
     import numpy as np
     eng = st.eng
-    npts, nvox = st.counts(params)
-    (gx, gy, gz), ncells = eng.grid_size()
+    if full:
+        npts, nvox = st.counts(params)
     eng.set_pipeline_depth(depth)
     pc = params.to_c(None, None, False, False)
     # prime: a slot captures its graph on its second steady frame; 2 rounds over the slots + 1
@@ -342,23 +415,8 @@ def time_single(st, params, steps, warmup, depth, kernel_timing, pmc_key, batch=
     st.run(pc, prime + warmup, steps, batch)
     eng.synchronize()
     elapsed = time.perf_counter() - t0
-    idx = [((prime + warmup + i) * batch + j) % st.ring for i in range(steps) for j in range(batch)]
-    n_avg = float(np.mean([npts[i] for i in idx]))
-    g_avg = float(np.mean([nvox[i] for i in idx]))
-    s_avg, runs, snap = st.sort_items(params, batch)
-    mb = model_bytes(st.P, n_avg, g_avg, ncells, batch, s_avg, runs, snap)
-    roof = None
-    if kernel_timing:
-        kt_steps = min(steps, 200)
-        eng.set_pipeline_depth(1)  # one frame in flight: launch durations without overlap
-        eng.set_profiling(True)
-        st.run(pc, prime + warmup, kt_steps, batch)
-        eng.synchronize()
-        kt = eng.kernel_times()
-        eng.set_profiling(False)
-        roof = roofline_from(kt, kt_steps, mb, pmc_key)
-    # SURVEY.md §8(d) B_alg per frame, times the frames of a step
-    survey = batch * (2.0 * st.P + 24.0 * n_avg + 9.0 * ncells)
+    dumped = dump_outputs(eng, batch, dump_dir) if dump_dir else None
+    (gx, gy, gz), ncells = eng.grid_size()
     # bytes the step actually moves (PMC FETCH x2 + WRITE of every kernel of a steady step, one
     # batch in flight, profiles/pmc_traffic.json) over the measured step time
     step_pmc = pmc_record(pmc_key).get("_step", {}).get("hbm_bytes_per_step")
@@ -367,22 +425,45 @@ def time_single(st, params, steps, warmup, depth, kernel_timing, pmc_key, batch=
         gbps = step_pmc * steps / elapsed / 1e9
         pmc_line = {"step_pmc_bytes": step_pmc, "step_pmc_GBps": round(gbps, 2),
                     "step_pmc_frac": round(gbps / HBM_PEAK_GBPS, 4)}
-    return {
+    line = {
         "value": round(st.P * batch * steps / elapsed / 1e6, 3),
         "ms_per_step": round(elapsed / steps * 1e3, 5),
         "frames_per_step": batch, "ms_per_frame": round(elapsed / steps / batch * 1e3, 5),
         "steps": steps, "warmup": warmup, "prime": prime,
+        "grid": [gx, gy, gz], "grid_cells": ncells, "frames_in_flight": depth,
+        **pmc_line,
+        "roofline": None,
+    }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
+    if not full:
+        return line
+    idx = [((prime + warmup + i) * batch + j) % st.ring for i in range(steps) for j in range(batch)]
+    n_avg = float(np.mean([npts[i] for i in idx]))
+    g_avg = float(np.mean([nvox[i] for i in idx]))
+    s_avg, runs, snap = st.sort_items(params, batch)
+    mb = model_bytes(st.P, n_avg, g_avg, ncells, batch, s_avg, runs, snap)
+    if kernel_timing:
+        kt_steps = min(steps, 200)
+        eng.set_pipeline_depth(1)  # one frame in flight: launch durations without overlap
+        eng.set_profiling(True)
+        st.run(pc, prime + warmup, kt_steps, batch)
+        eng.synchronize()
+        kt = eng.kernel_times()
+        eng.set_profiling(False)
+        line["roofline"] = roofline_from(kt, kt_steps, mb, pmc_key)
+    # SURVEY.md §8(d) B_alg per frame, times the frames of a step
+    survey = batch * (2.0 * st.P + 24.0 * n_avg + 9.0 * ncells)
+    line.update({
         "points_per_frame_after_crop": round(n_avg), "voxels_per_frame": round(g_avg),
         "survival_after_crop": round(n_avg / st.P, 4),
-        "grid": [gx, gy, gz], "grid_cells": ncells, "frames_in_flight": depth,
         "step_survey_bytes": round(survey),
         "step_survey_GBps": round(survey * steps / elapsed / 1e9, 2),
         "step_survey_frac": round(survey * steps / elapsed / 1e9 / HBM_PEAK_GBPS, 4),
         "step_survey_note": "SURVEY 8(d) B_alg (counts a u32 history this build never moves)",
-        **pmc_line,
         "model_bytes_per_launch": {k: round(v) for k, v in mb.items()},
-        "roofline": roof,
-    }
+    })
+    return line
 
 
 def cgroup_cpu_quota():
@@ -519,6 +600,10 @@ def main():
     # the one-JSON-line contract: fd 1 points at stderr for the run, the line goes to the original.
     global _JSON_FD
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.dist or args.h2d_only
+                              or "WORLD_SIZE" in os.environ):
+        raise SystemExit("bench: --dump-outputs writes the single-GPU path's outputs (--gpus 1, "
+                         "no --dist, no --h2d-only)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.transport == "rccl":
         sys.exit(launch_ranks(args))  # (no GPU call has been made in this process)
     sys.stdout.flush()
@@ -563,17 +648,18 @@ def main():
 
     if dist is None:
         line = time_single(st, params, args.steps, args.warmup, max(1, min(4, args.pipeline)),
-                           not args.no_kernel_timing, pmc_key, max(1, args.batch))
+                           args.full and not args.no_kernel_timing, pmc_key, max(1, args.batch),
+                           full=args.full, dump_dir=args.dump_outputs)
         cfg_extra = {"parallelism": "single GPU", "exchange": None}
     else:
         line, cfg_extra = time_multi(args, st, params, dist, world, pmc_key)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(st, params, args.cpu_seconds)
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         secondary = run_secondary(args, params)
 
     if rank == 0:
@@ -737,7 +823,7 @@ def time_multi(args, st, params, dist, world, pmc_key):
                                       else "the last rank holds the rollbuffer (SURVEY 8(e))",
                               "balance": "gpu_ms_per_step_per_rank: each rank's event-timed GPU "
                                          "work per step"}
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         kt_steps = min(args.steps, 100)
         if depth > 1:
             eng.synchronize()
