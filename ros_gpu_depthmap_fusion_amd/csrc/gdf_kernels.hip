@@ -485,6 +485,28 @@ __device__ __forceinline__ bool beyond_max_distance(float pp) {
     return pp > __uint_as_float(0x42C80001u);
 }
 
+// The crop stage of the px mask kernels: the box read from the kernel arguments ONCE per kernel
+// (every further read of FrameArgs counts against the compiler's bound for addressing the by-value
+// arguments in place; past it the kernel keeps a private copy - cam_table's note), then
+// crop_points on the camera-frame point of a pixel: depth_bits' crop stage, the same rows of Tc,
+// the same comparisons (a NaN coordinate is inside); true when the crop is off
+struct CropBox {
+    bool on;
+    float lo[3], hi[3];
+};
+__device__ __forceinline__ CropBox crop_box(const FrameArgs& a) {
+    return CropBox{a.do_crop != 0, {a.lo[0], a.lo[1], a.lo[2]}, {a.hi[0], a.hi[1], a.hi[2]}};
+}
+__device__ __forceinline__ bool crop_in(const CropBox& b, const CamDesc& c, float x, float y,
+                                        float z) {
+    if (!b.on) return true;
+    const float qx = mrow(c.Tc + 0, x, y, z, 1.0f);
+    const float qy = mrow(c.Tc + 4, x, y, z, 1.0f);
+    const float qz = mrow(c.Tc + 8, x, y, z, 1.0f);
+    return !((qx < b.lo[0]) | (qx > b.hi[0]) | (qy < b.lo[1]) | (qy > b.hi[1]) |
+             (qz < b.lo[2]) | (qz > b.hi[2]));
+}
+
 // check_at / check_at_rot45 (filter_flying_pixels.glsl:74-96) on four neighbour points: invalid
 // if any neighbour has depth 0 or dot(normalize(cross(down - up, right - left)), n) < thr with
 // n = -normalize(p).  The exact value cv is decided first by the filter
@@ -1044,11 +1066,16 @@ __global__ __launch_bounds__(1024) void k_mask(FrameArgs a) {
 // x0 + i + j * blockDim (blockDim = 256 / PX).  Pixel 0 is k_mask's kInterior / kRowStart wave
 // of the segment's first columns, the others are interior whenever pixel 0's row is.  One
 // wave-uniform ring exit and the exact-fallback ballots of a ring serve all PX pixels; the
-// arithmetic of each pixel is depth_bits' (same operations, same order).
+// arithmetic of each pixel is depth_bits' (same operations, same order).  The STAGES are not in
+// depth_bits' order: these kernels publish only bit 2 (flying filter AND crop), so the crop of the
+// centre point is evaluated first and a pixel outside the box never enters the rings (about 44 %
+// of the bench frames' waves hold no other pixel and leave at the first ring's ballot,
+// tools/crop_stats.py).  Bits: 0 = depth valid, 2 = kept; bit 1 is not produced here.
 template <int AMODE, int PX>
-__device__ __forceinline__ void depth_bits_px(const FrameArgs& a, const CamDesc* cams, int k,
-                                              const Band& t, const float* s_yn, const uint32_t* x,
-                                              uint32_t y, const bool* in, uint32_t* bits) {
+__device__ __forceinline__ void depth_bits_px(const FrameArgs& a, const CropBox& box,
+                                              const CamDesc* cams, int k, const Band& t,
+                                              const float* s_yn, const uint32_t* x, uint32_t y,
+                                              const bool* in, uint32_t* bits) {
     const CamDesc& c = cams[k];
     const int h = t.h;
     const float scale = c.scale;
@@ -1060,7 +1087,8 @@ __device__ __forceinline__ void depth_bits_px(const FrameArgs& a, const CamDesc*
         p[j] = in[j] ? band_pt(t, h, x[j], s_yn[h], scale) : P3{0.f, 0.f, 0.f, false};
         conv[j] = in[j] & p[j].v;
         const float pp = dot3(p[j].x, p[j].y, p[j].z, p[j].x, p[j].y, p[j].z);
-        fly[j] = conv[j] & !beyond_max_distance(pp);
+        // (crop first, as depth_bits_px2: a cropped pixel is not live, but stays a neighbour)
+        fly[j] = conv[j] & !beyond_max_distance(pp) & crop_in(box, c, p[j].x, p[j].y, p[j].z);
         const float rr = __builtin_amdgcn_rsqf(pp);
         nx[j] = -(p[j].x * rr);
         ny[j] = -(p[j].y * rr);
@@ -1086,18 +1114,9 @@ __device__ __forceinline__ void depth_bits_px(const FrameArgs& a, const CamDesc*
                                         p[j].z, fly[j]);
         }
     }
+    // (bit 1, the flying filter without the crop, is not computed here: fly already holds the crop)
 #pragma unroll
-    for (int j = 0; j < PX; ++j) {
-        bool crop = true;
-        if (a.do_crop) {
-            const float qx = mrow(c.Tc + 0, p[j].x, p[j].y, p[j].z, 1.0f);
-            const float qy = mrow(c.Tc + 4, p[j].x, p[j].y, p[j].z, 1.0f);
-            const float qz = mrow(c.Tc + 8, p[j].x, p[j].y, p[j].z, 1.0f);
-            crop = !((qx < a.lo[0]) | (qx > a.hi[0]) | (qy < a.lo[1]) | (qy > a.hi[1]) |
-                     (qz < a.lo[2]) | (qz > a.hi[2]));
-        }
-        bits[j] = (uint32_t)conv[j] | ((uint32_t)fly[j] << 1) | ((uint32_t)(fly[j] & crop) << 2);
-    }
+    for (int j = 0; j < PX; ++j) bits[j] = (uint32_t)conv[j] | ((uint32_t)fly[j] << 2);
 }
 
 // ---- the two pixels of a thread in packed f32 (v_pk_mul_f32 / v_pk_add_f32) --------------------
@@ -1201,9 +1220,10 @@ __device__ __forceinline__ void voxel_key2(f2v px, f2v py, f2v pz, const float* 
 }
 
 template <int AMODE>
-__device__ __forceinline__ void depth_bits_px2(const FrameArgs& a, const CamDesc* cams, int k,
-                                               const Band& t, const float* s_yn, const uint32_t* x,
-                                               uint32_t y, const bool* in, uint32_t* bits) {
+__device__ __forceinline__ void depth_bits_px2(const FrameArgs& a, const CropBox& box,
+                                               const CamDesc* cams, int k, const Band& t,
+                                               const float* s_yn, const uint32_t* x, uint32_t y,
+                                               const bool* in, uint32_t* bits) {
     const CamDesc& c = cams[k];
     const int h = t.h;
     const float scale = c.scale;
@@ -1215,8 +1235,12 @@ __device__ __forceinline__ void depth_bits_px2(const FrameArgs& a, const CamDesc
     if (!in[1]) { p.x.y = 0.f; p.y.y = 0.f; p.z.y = 0.f; p.v1 = false; }
     const bool conv0 = in[0] & p.v0, conv1 = in[1] & p.v1;
     const f2v pp = (p.x * p.x + p.y * p.y) + p.z * p.z;
-    bool fly0 = conv0 & !beyond_max_distance(pp.x);
-    bool fly1 = conv1 & !beyond_max_distance(pp.y);
+    // crop first: the kernel publishes fly & crop only, so the rings of a pixel the crop discards
+    // decide nothing - it leaves the live set here (and a wave of such pixels the ring loop at
+    // its first ballot).  It stays a NEIGHBOUR of the others: the rings read the band, not this.
+    const bool crop0 = crop_in(box, c, p.x.x, p.y.x, p.z.x), crop1 = crop_in(box, c, p.x.y, p.y.y, p.z.y);
+    bool fly0 = conv0 & !beyond_max_distance(pp.x) & crop0;
+    bool fly1 = conv1 & !beyond_max_distance(pp.y) & crop1;
     const f2v rr = f2(__builtin_amdgcn_rsqf(pp.x), __builtin_amdgcn_rsqf(pp.y));
     const f2v nx = -(p.x * rr), ny = -(p.y * rr), nz = -(p.z * rr);
     const int x0 = (int)x[0], x1 = (int)x[1];
@@ -1237,20 +1261,9 @@ __device__ __forceinline__ void depth_bits_px2(const FrameArgs& a, const CamDesc
         fly0 = fly0 & r0;
         fly1 = fly1 & r1;
     }
-    const bool fl[2] = {fly0, fly1}, cv[2] = {conv0, conv1};
-    const float qxv[2] = {p.x.x, p.x.y}, qyv[2] = {p.y.x, p.y.y}, qzv[2] = {p.z.x, p.z.y};
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        bool crop = true;
-        if (a.do_crop) {
-            const float qx = mrow(c.Tc + 0, qxv[j], qyv[j], qzv[j], 1.0f);
-            const float qy = mrow(c.Tc + 4, qxv[j], qyv[j], qzv[j], 1.0f);
-            const float qz = mrow(c.Tc + 8, qxv[j], qyv[j], qzv[j], 1.0f);
-            crop = !((qx < a.lo[0]) | (qx > a.hi[0]) | (qy < a.lo[1]) | (qy > a.hi[1]) |
-                     (qz < a.lo[2]) | (qz > a.hi[2]));
-        }
-        bits[j] = (uint32_t)cv[j] | ((uint32_t)fl[j] << 1) | ((uint32_t)(fl[j] & crop) << 2);
-    }
+    // (bit 1, the flying filter without the crop, is not computed here: fly already holds the crop)
+    bits[0] = (uint32_t)conv0 | ((uint32_t)fly0 << 2);
+    bits[1] = (uint32_t)conv1 | ((uint32_t)fly1 << 2);
 }
 
 // emit partition: the part (key range) of voxel key k (part_of below: whole occupancy-mark words)
@@ -1435,14 +1448,15 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
                 x[j] = sg.x0 + i + (uint32_t)NT * j;
                 in[j] = i + (uint32_t)NT * j < sg.len;
             }
+            const CropBox box = crop_box(a);
             if (PX == 2 && a.mask_packed && sg.y >= 4u && xw0 >= 4u)
-                depth_bits_px2<kInterior>(a, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
+                depth_bits_px2<kInterior>(a, box, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
             else if (PX == 2 && a.mask_packed && wrap)
-                depth_bits_px2<kRowStart>(a, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
+                depth_bits_px2<kRowStart>(a, box, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
             else if (sg.y >= 4u && xw0 >= 4u)
-                depth_bits_px<kInterior, PX>(a, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
+                depth_bits_px<kInterior, PX>(a, box, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
             else if (wrap)
-                depth_bits_px<kRowStart, PX>(a, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
+                depth_bits_px<kRowStart, PX>(a, box, s_cams, 0, t, s_ynr, x, sg.y, in, bits);
             else
 #pragma unroll
                 for (int j = 0; j < PX; ++j)
@@ -1885,7 +1899,9 @@ __global__ __launch_bounds__(1024) void k_emit(FrameArgs a) {
 // k_emit for 256-pixel segments with two pixels per thread (x, x + 128; 128 threads per
 // segment, k_mask_px's layout: pixel j of wave w is validity word w + 2j): the block's scalar
 // work (camera lookup, counts and run prefixes of the segment's words) is shared by twice the
-// pixels per wave.  Same outputs in the same order as k_emit.
+// pixels per wave.  Same outputs in the same order as k_emit.  A segment whose validity words are
+// all zero ends after the first scalar-load round (k_emit_px2 below; not the partition's kernel,
+// whose per-part offsets and counters are set up before its camera lookup).
 // k_emit_px2 under the emit partition (FrameArgs::nparts): the same points, keys and marks; each
 // kept point goes to its part (the segment's offset of the part from the one scan over [points
 // per part | runs per part][segment], then the part's earlier words, then its rank among the
@@ -2008,20 +2024,54 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2(FrameArgs a) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     constexpr int NT = SEGW / 2, NW = NT / 64, NWORDS = SEGW / 64;
     const uint32_t s = blockIdx.x;
-    for (uint32_t j = threadIdx.x; j < (1u << kMarkCacheBits); j += NT) s_mark[j] = 0xFFFFFFFFu;
+    // the segment's validity words: a block-uniform address, so scalar loads - issued with the
+    // descriptor fields of the camera lookup, one scalar-load round for both
+    uint64_t vw[NWORDS];
+#pragma unroll
+    for (int w = 0; w < NWORDS; ++w) vw[w] = G(a.vbits)[(size_t)s * 16 + w];
     const gptr<const CamDesc> cams = G(cam_table(a));
+    int k = seg_camera(cams, a.ncams, s, a.seg_uniform);
+    k = __builtin_amdgcn_readfirstlane(k);
+    const uint32_t seg0 = cams[k].seg0, nchunk = cams[k].nchunk, segw = cams[k].segw;
+    const uint32_t W = cams[k].W, fr = cams[k].frame;
+    const uint16_t* const cdepth = cams[k].depth;
+    const float* const cxn = cams[k].xn;
+    const float* const cyn = cams[k].yn;
+    const uint32_t nblk = gridDim.x;
+    uint32_t* const fps = a.frame_pt_start;
+    // (the fields in registers before the branch below: the compiler otherwise sinks their loads
+    // behind it, a second dependent round for every segment that stays)
+    asm volatile("" ::"s"(seg0), "s"(nchunk), "s"(segw), "s"(W), "s"(fr), "s"(cdepth), "s"(cxn),
+                 "s"(cyn), "s"(nblk), "s"(fps));
+    uint64_t any = 0;
+#pragma unroll
+    for (int w = 0; w < NWORDS; ++w) {
+        // (the words pass through an empty statement after the one above: their first use - and
+        // with it the wait for the scalar loads - stays behind the issue of the fields' loads)
+        asm volatile("" : "+s"(vw[w]));
+        any |= vw[w];
+    }
+    // An empty segment writes no point, key, run record, mark or histogram count: its block
+    // leaves here, before the depth / ray-factor / offset loads, the barrier and the prefix -
+    // unless it has a duty that needs the prefix: the last block (out_count, run_count, the
+    // closing run_start, frame_pt_start's end) and a frame's first segment (frame_pt_start).
+    if (!__builtin_amdgcn_readfirstlane((uint32_t)(any | (any >> 32))) && s != nblk - 1) {
+        if (!fps) return;
+        const bool first_of_frame =
+            s == seg0 && (k == 0 || !cams[k - 1].emit || cams[k - 1].frame != fr);
+        if (!first_of_frame) return;
+    }
+    for (uint32_t j = threadIdx.x; j < (1u << kMarkCacheBits); j += NT) s_mark[j] = 0xFFFFFFFFu;
     const bool hist = a.key_hist && !a.run_mode;
     if (hist)
         for (uint32_t i = threadIdx.x; i < radix_hist_span(a.npasses); i += NT) s_hist[i] = 0;
     GroupPart gp{};
     if (!a.fused_prefix && a.grp_tot) gp = group_partials_issue(a, s);
     const uint32_t i = threadIdx.x;
-    int k = seg_camera(cams, a.ncams, s, a.seg_uniform);
-    k = __builtin_amdgcn_readfirstlane(k);
-    const uint32_t j = s - cams[k].seg0;
-    const uint32_t y = j / cams[k].nchunk;
-    const uint32_t x0 = (j - y * cams[k].nchunk) * cams[k].segw;
-    const uint32_t len = min(cams[k].segw, cams[k].W - x0);
+    const uint32_t j = s - seg0;
+    const uint32_t y = j / nchunk;
+    const uint32_t x0 = (j - y * nchunk) * segw;
+    const uint32_t len = min(segw, W - x0);
     uint64_t m[2];
     uint32_t dval[2] = {0u, 0u};
     float xnv[2] = {0.0f, 0.0f};
@@ -2031,10 +2081,13 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2(FrameArgs a) {
     float xl[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        m[q] = G(a.vbits)[(size_t)s * 16 + wid + NW * q];
+        m[q] = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w)  // (word wid + NW q of the words already here)
+            if (w == wid) m[q] = vw[w + NW * q];
         const uint32_t ic = min(i + (uint32_t)NT * q, len - 1u);
-        dl[q] = G(cams[k].depth)[y * cams[k].W + x0 + ic];
-        xl[q] = G(cams[k].xn)[x0 + ic];
+        dl[q] = G(cdepth)[y * W + x0 + ic];
+        xl[q] = G(cxn)[x0 + ic];
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -2042,12 +2095,12 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2(FrameArgs a) {
         dval[q] = in ? dl[q] : 0u;
         xnv[q] = in ? xl[q] : 0.0f;
     }
-    const float ynv = G(cams[k].yn)[y];
+    const float ynv = G(cyn)[y];
     // counts (and runs) of the segment's 4 words: the prefix of each of this thread's words
     uint32_t pc[NWORDS], rc[NWORDS];
 #pragma unroll
     for (int w = 0; w < NWORDS; ++w) {
-        pc[w] = (uint32_t)__popcll(G(a.vbits)[(size_t)s * 16 + w]);
+        pc[w] = (uint32_t)__popcll(vw[w]);
         rc[w] = 0u;
     }
     const uint32_t sbase = a.fused_prefix ? 0u : G(a.seg_offsets)[s];
@@ -2082,10 +2135,9 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2(FrameArgs a) {
             *G(a.run_count) = rbase + rtot;
         }
     }
-    const uint32_t fr = cams[k].frame;
     if (a.frame_pt_start && threadIdx.x == 0) {
         const bool first_of_frame =
-            s == cams[k].seg0 && (k == 0 || !cams[k - 1].emit || cams[k - 1].frame != fr);
+            s == seg0 && (k == 0 || !cams[k - 1].emit || cams[k - 1].frame != fr);
         if (first_of_frame) G(a.frame_pt_start)[fr] = base;
         if (s == gridDim.x - 1) G(a.frame_pt_start)[a.nframes] = base + tot;
     }
