@@ -34,9 +34,10 @@ extern "C" {
  * caller checks gdf_version() against the header it was built with (the Python binding and the
  * C++ facade do).  0.2: gdf_frame_params.defer_voxelize, frames_per_rank of
  * gdf_union_occupancy_pairs; 0.3: batched take / sparse per-frame grids; 0.4: slot selection
- * (gdf_get_slot / gdf_select_slot), build provenance (gdf_build_info). */
+ * (gdf_get_slot / gdf_select_slot), build provenance (gdf_build_info); 0.5: the last frame's
+ * compaction kernels (gdf_get_frame_kernels). */
 #define GDF_VERSION_MAJOR 0
-#define GDF_VERSION_MINOR 4
+#define GDF_VERSION_MINOR 5
 
 #define GDF_MAX_CAMERAS 16
 
@@ -505,6 +506,14 @@ int gdf_get_kernel_times(gdf_engine* engine, double* ms_sum, uint64_t* launches,
  * keeps the snapshot taken at gdf_create - engines created under other environments never retune
  * it - and gdf_create logs a non-empty one to stderr. */
 int gdf_get_tuning(gdf_engine* engine, char* buf, uint32_t capacity);
+
+/* The two kernels of the engine's most recent depth compaction, as "mask=<name> emit=<name>"
+ * (for example "mask=k_mask_px_o8<2,256> emit=k_emit_px2<256>"; "" before any frame and after a
+ * frame without depth maps).  The names are those the engine resolved for that frame's launch
+ * arguments - directly launched, captured or replayed from a graph, single frame or batch, the
+ * emit partition included - so a caller (a test) can tell which compaction path it ran.  Buffer
+ * convention of gdf_get_tuning. */
+int gdf_get_frame_kernels(gdf_engine* engine, char* buf, uint32_t capacity);
 
 /* ---- debug / parity hooks ------------------------------------------------------------------ */
 /* Keep per-point stage masks of the next compaction launch: bit0 = valid after convert

@@ -524,6 +524,8 @@ struct gdf_engine {
 
     Tuning tune;                    // launch shapes, a snapshot at gdf_create
     std::string tuning_set;         // the GDF_* tuning variables set at creation ("K=V K=V")
+    // the last depth compaction's kernels, null without one (gdf_get_frame_kernels)
+    const void *frame_mask = nullptr, *frame_emit = nullptr;
     int sort_pt = 0;  // radix keys per thread (4, 8, 16); 0: chosen by frame capacity
     uint32_t sel_segs = kSelSegs, sel_threads = kSelThreads;  // k_sel tile shape
     bool sel_shape_set = false;     // GDF_SEL_SHAPE given (else the shape follows the window)
@@ -1612,9 +1614,17 @@ void frame_launched(gdf_engine* e, bool fused_voxel, bool key_hist, bool runs = 
     e->sl().vox_valid = false;
 }
 
+// the kernels launch_frame resolves for these arguments, direct or captured (a graph replay runs
+// the kernels of the capture with the same key): kept for gdf_get_frame_kernels
+void note_frame_kernels(gdf_engine* e, const FrameArgs& a) {
+    e->frame_mask = a.total_segs ? mask_kernel(a) : nullptr;
+    e->frame_emit = a.total_segs ? emit_kernel(a) : nullptr;
+}
+
 void run_frame(gdf_engine* e, bool fused_voxel, bool compaction_marks = false) {
     e->sl().pf_valid = false;
     const FrameArgs a = frame_args(e, fused_voxel, compaction_marks);
+    note_frame_kernels(e, a);
     e->sl().part_emitted = a.nparts != 0;
     if (e->profiling) e->timed(GDF_KERNEL_EVENT_FLOOR, [] {});  // calibrates the event overhead
     e->timed(GDF_KERNEL_FRAME, [&] { HIPCHK(launch_frame(a, e->s(), e->hook_ptr())); });
@@ -1886,6 +1896,7 @@ void prefetch_downloads(gdf_engine* e, hipStream_t st, uint32_t parts) {
 
 void run_fused_frame(gdf_engine* e, int average, uint32_t lifetime) {
     const FrameArgs a = frame_args(e, true);
+    note_frame_kernels(e, a);
     frame_launched(e, true, a.key_hist != nullptr, a.run_mode != 0);  // (the launches below follow)
     const VoxelizeArgs v = voxelize_args(e, average, (int)lifetime);
     Slot::Graphs& G = e->sl().graph;
@@ -2188,6 +2199,21 @@ int gdf_get_tuning(gdf_engine* e, char* buf, uint32_t capacity) {
         return GDF_ERR_CAPACITY;
     }
     std::memcpy(buf, e->tuning_set.c_str(), e->tuning_set.size() + 1);
+    return GDF_OK;
+}
+
+int gdf_get_frame_kernels(gdf_engine* e, char* buf, uint32_t capacity) {
+    ENGINE_OR_FAIL(e);
+    if (!buf || capacity == 0) return GDF_ERR_ARG;
+    std::string s;
+    if (e->frame_mask)
+        s = std::string("mask=") + compaction_kernel_name(e->frame_mask) +
+            " emit=" + compaction_kernel_name(e->frame_emit);
+    if (s.size() + 1 > capacity) {
+        g_last_error = "frame kernels: buffer too small";
+        return GDF_ERR_CAPACITY;
+    }
+    std::memcpy(buf, s.c_str(), s.size() + 1);
     return GDF_OK;
 }
 

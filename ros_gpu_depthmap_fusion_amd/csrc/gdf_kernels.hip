@@ -2577,6 +2577,30 @@ const void* emit_kernel(const FrameArgs& a) {
     return reinterpret_cast<const void*>(&k_emit);
 }
 
+// the names of every kernel mask_kernel / emit_kernel can return (gdf_get_frame_kernels): one
+// table, keyed on those pointers; a kernel missing from it is reported as "?"
+const char* compaction_kernel_name(const void* k) {
+    static const struct {
+        const void* k;
+        const char* name;
+    } names[] = {
+        {reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>), "k_mask_px_o8<2,256>"},
+        {reinterpret_cast<const void*>(&k_mask_px<2, 256>), "k_mask_px<2,256>"},
+        {reinterpret_cast<const void*>(&k_mask_px<2, 640>), "k_mask_px<2,640>"},
+        {reinterpret_cast<const void*>(&k_mask<false, 4>), "k_mask<false,4>"},
+        {reinterpret_cast<const void*>(&k_mask<true, 4>), "k_mask<true,4>"},
+        {reinterpret_cast<const void*>(&k_mask<false, 0>), "k_mask<false,0>"},
+        {reinterpret_cast<const void*>(&k_mask<true, 0>), "k_mask<true,0>"},
+        {reinterpret_cast<const void*>(&k_emit_px2_parts<256>), "k_emit_px2_parts<256>"},
+        {reinterpret_cast<const void*>(&k_emit_px2<256>), "k_emit_px2<256>"},
+        {reinterpret_cast<const void*>(&k_emit_px2<640>), "k_emit_px2<640>"},
+        {reinterpret_cast<const void*>(&k_emit), "k_emit"},
+    };
+    for (const auto& n : names)
+        if (n.k == k) return n.name;
+    return "?";
+}
+
 const void* frame_kernel(int which, int rot45, uint32_t F) {
     if (which == 1) return reinterpret_cast<const void*>(&k_emit);
     if (which == 2) return reinterpret_cast<const void*>(&k_sel<8>);

@@ -50,6 +50,7 @@ bool sel_key_lds_allowed(uint32_t bytes);  // k_sel's key stash fits (and is ena
 const void* mask_kernel(const FrameArgs& a);  // the compaction pass-1 kernel launch_frame uses
 const void* emit_kernel(const FrameArgs& a);  // the compaction pass-2 kernel launch_frame uses
 bool emit_partition_kernels(const FrameArgs& a);
+const char* compaction_kernel_name(const void* k);  // of a mask_kernel / emit_kernel result
 
 // filter_point_sequence + insert into the rollbuffer ring (w = mask): new points
 // [src0, src0 + cnt) (all by default) of the n uploaded, their filter neighbours over all n

@@ -149,6 +149,7 @@ EXPORTED = [
     "gdf_mask_dilate", "gdf_transform_points", "gdf_add_halo_depthmap_device",
     "gdf_partition_points", "gdf_voxelize_points", "gdf_partition_runs", "gdf_voxelize_runs", "gdf_voxelize_runs_marked", "gdf_voxelize_runs_recv", "gdf_set_partition_marks", "gdf_set_emit_partition", "gdf_set_partition_segments", "gdf_last_sort_items", "gdf_get_stream",
     "gdf_get_graph_stats", "gdf_get_slot", "gdf_select_slot", "gdf_build_info", "gdf_get_tuning",
+    "gdf_get_frame_kernels",
     "gdf_download_frame", "gdf_set_slot_streams",
     # include/gdf_fused.h: a rank of the multi-GPU fused cloud in C++ over RCCL
     "gdf_fused_unique_id", "gdf_fused_create", "gdf_fused_destroy", "gdf_fused_halo_pixels",
@@ -164,7 +165,7 @@ EXPORTED = [
 ]
 
 
-ABI_VERSION = (0, 4)  # include/gdf.h GDF_VERSION_MAJOR / _MINOR
+ABI_VERSION = (0, 5)  # include/gdf.h GDF_VERSION_MAJOR / _MINOR
 
 
 def load_library(path: str = LIB_PATH):
@@ -258,6 +259,7 @@ def load_library(path: str = LIB_PATH):
         "gdf_select_slot": (i32, [vp, i32]),
         "gdf_build_info": (C.c_char_p, []),
         "gdf_get_tuning": (i32, [vp, C.c_char_p, u32]),
+        "gdf_get_frame_kernels": (i32, [vp, C.c_char_p, u32]),
         "gdf_download_frame": (i32, [vp, u32, P(HostFrame)]),
         "gdf_set_slot_streams": (i32, [vp, vp, i32]),
         "gdf_fused_unique_id": (i32, [C.c_char_p, vp]),
@@ -900,6 +902,13 @@ class GPUDepthmapFusion:
         buf = C.create_string_buffer(4096)
         self._check(self._lib.gdf_get_tuning(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def frame_kernels(self) -> dict:
+        """gdf_get_frame_kernels: the kernels of the most recent depth compaction, {"mask": name,
+        "emit": name} ({} before any frame and after a frame without depth maps)."""
+        buf = C.create_string_buffer(256)
+        self._check(self._lib.gdf_get_frame_kernels(self._h, buf, len(buf)))
+        return dict(kv.split("=", 1) for kv in buf.value.decode().split())
 
     def last_sort_items(self):
         """(items, runs): what the last synchronous processFrame's voxelize sorted - runs of

@@ -2,50 +2,58 @@
 empty segment after its first load round (bar: bit-exact against the oracle, as
 test_gpu_round4.py).
 
-Hand-built depth maps put every shape of "nothing kept" where the two changes act, and each
-scene ASSERTS FROM THE ORACLE'S STAGE ARRAYS, on the CPU, that it holds what it is meant to hold
-(scene_contents):
+The scenes are 448 pixels wide and run under GDF_SEG_ITEMS=256: rows in segments of 256 + 192,
+the launch the px kernels take (k_mask_px_o8<2,256> / k_mask_px<2,256> + k_emit_px2<256>, thread
+t of a segment at x0 owning the pixels x0 + t and x0 + t + 128).  Every case asserts FIRST, from
+the engine's frame_kernels(), that those kernels ran: at their first width, 320 without the knob,
+these scenes were one 320-pixel segment per row and ran k_mask<false,4> + k_emit - neither kernel
+the file was written for.  That run is kept: every case runs its scene at 448 and then, without
+the knob, at 320 x 32 (valid coverage of k_mask), with those kernels asserted too.
+
+Hand-built depth maps (tests/px_scenes.py) put every shape of "nothing kept" where the two changes
+act, and each scene ASSERTS FROM THE ORACLE'S STAGE ARRAYS, on the CPU, that it holds what it is
+meant to hold (px_scenes.crop_scene_contents; without a GPU: test_px_scenes.py):
 
   1  a segment in the middle of a frame with every pixel valid and flying-clean but outside the
-     crop (emit's early exit, mask's ring skip);
+     crop (emit's early exit, mask's ring skip), as a row's first and as its last segment;
   2  the same for the first segment of a frame other than frame 0 of a batch and for the last
      segment of the batch's last frame - the two blocks with a duty that must not exit;
   3  a segment where wave 0's 128 pixels (columns 0..63, 128..191) are cropped and wave 1 keeps
-     pixels;
+     pixels - and the same in the row's 192-pixel segment (wave 0: 256..319, 384..447; wave 1:
+     320..383, its second pixels past the row's end);
   4  kept pixels with depth-valid neighbours outside the crop within 4 pixels (>= 50): a cropped
      pixel still serves as a ring neighbour;
   5  a segment empty because its depth is zero, and one empty by the flying filter alone;
   6  a frame with the crop off (box +-1e9);
-  7  a frame of two 320 x 16 cameras (the empty-segment exit behind the lane-ballot camera lookup,
+  7  a frame of two 448 x 16 cameras (the empty-segment exit behind the lane-ballot camera lookup,
      with and without the lookup by division);
   8  every scene in run mode (GDF_FORCE_RUNS=1) and in points mode;
-  9  scene 3 also with GDF_NO_MASK_PACKED=1 (the scalar px form).
+  9  scene 3 also with GDF_NO_MASK_PACKED=1 (the scalar px form) and GDF_MASK_OCC8=0;
+  10 the batch through gdf_set_emit_partition (k_emit_px2_parts<256>: empty segments under the
+     partition's bookkeeping), 1 and 3 parts.
 
-"Flying-clean" is asserted where the image allows it: at W = 320 every segment touches a border
-of its row (columns 0..3 read their left neighbours from the previous row's end, columns
-W-4..W-1 fail the filter's bounds test), and so do a frame's first and last rows; the segments of
-1 are clean in every column 4..W-5, those of 2 (row 0, row H-1) are valid and outside the crop.
+"Flying-clean" is asserted where the image allows it: columns 0..3 read their left neighbours
+from the previous row's end, columns W-4..W-1 fail the filter's bounds test, and so do a frame's
+first and last rows; the segments of 1 are clean in every column 4..W-5, those of 2 (row 0, row
+H-1) are valid and outside the crop.
 
 The last test pins k_mask's debug stage masks (bits 0, 1, 2) at the launch defaults.
 """
-import functools
-import os
-
 import numpy as np
 import pytest
 
-from drive import compare_results, stagewise_frame
+import px_scenes as S
+from drive import (compare_frames, compare_results, engine_with, run_batch, stagewise_frame,
+                   voxelize_parts_and_compare)
 from oracle import OracleFusion
+from px_scenes import cam_args
 from ros_gpu_depthmap_fusion_amd import synth
 from ros_gpu_depthmap_fusion_amd.gdf import ComponentParams
 
 pytestmark = pytest.mark.gpu
 
-W, H = 320, 32
-SEG = 256  # the px kernels' segment; wave w owns columns 64w..64w+63 and 128+64w..128+64w+63
-WAVE0 = np.r_[0:64, 128:192]
-WAVE1 = np.r_[64:128, 192:256]
-NEAR, PLANE = 1000, 3000  # mm: in front of the crop box (x < 2 m) / inside it
+RUNS, POINTS = {"GDF_FORCE_RUNS": "1"}, {}
+PACKED_OFF, OCC8_OFF = {"GDF_NO_MASK_PACKED": "1"}, {"GDF_MASK_OCC8": "0"}
 
 
 @pytest.fixture(scope="module")
@@ -53,228 +61,87 @@ def Engine(gpu_engine_factory):
     return gpu_engine_factory
 
 
-def cam_args(cam, depth):
-    return (depth, *cam.intrinsics(), cam.T_world, cam.T_crop)
+def layout(W):
+    """(the segment knob, the kernels it must select) of the scenes at width W."""
+    if W == 448:
+        return S.PX_ENV, {"mask": S.K_MASK_O8, "emit": S.K_EMIT_PX}
+    assert W == 320  # one 320-pixel segment per row: not the px kernels
+    return {}, {"mask": S.K_MASK, "emit": S.K_EMIT}
 
 
-def engine_with(Engine, **env):
-    """An engine created with the given GDF_* environment knobs (read at creation)."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return Engine()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+def run_and_compare(Engine, sc, W, knobs, tag, frames=None, ref=None):
+    env, want = layout(W)
+    if W == 448 and knobs.get("GDF_MASK_OCC8") == "0":
+        want = {"mask": S.K_MASK_PX, "emit": S.K_EMIT_PX}
+    gpu = engine_with(Engine, **env, **knobs)
+    for fr, rf in ([(sc.frames, sc.ref)] if frames is None else zip(frames, ref)):
+        run_batch(gpu, sc.params, fr)
+        assert gpu.frame_kernels() == want, (tag, gpu.frame_kernels(), gpu.tuning())
+        compare_frames(gpu, rf, tag)
 
 
-def box_params(lo, hi):
-    """Launch defaults with the crop box (lo, hi); the voxel grid keeps its default bounds."""
-    p = ComponentParams()
-    p.crop_min, p.crop_max = lo, hi
-    return p
+WIDTHS = (448, 320)  # the px layout, then the file's first width: k_mask + k_emit
 
 
-# The camera looks along world +x from 1 m above the ground: a fronto-parallel plane at depth d
-# has world x = d and z = 1 - yn d.  The box 2..6 x -20..20 x 0.8..1.1 therefore keeps the plane
-# at 3 m in rows 10..28 of a 32-row image (z of row v: 1 - 3 (v - 16) / 192) and crops rows 0..9
-# (too high) and 29..31 (too low) on a smooth surface - the flying filter passes across the cut.
-BATCH_BOX = ((2.0, -20.0, 0.8), (6.0, 20.0, 1.1))
-ROWS_KEPT = (10, 28)
-MID_ROW = 6           # scene 1: cropped, with clean rows 2..10 around it
-WAVE_ROWS = (12, 22)  # scene 3: rows whose wave-0 columns stand at 1 m
-ZERO_ROW, NOISE_ROW = 20, 25  # scene 5, frame 1
+@pytest.mark.parametrize("knobs", [POINTS, RUNS, PACKED_OFF, {**PACKED_OFF, **RUNS}, OCC8_OFF,
+                                   {**OCC8_OFF, **RUNS}])
+def test_batch_of_cropped_segments_matches_oracle(Engine, knobs):
+    """Scenes 1-5 in one 3-frame batch of W x 32 frames (8, 9: run and points mode, the packed
+    and the scalar px form, the 8-wave and the plain kernel)."""
+    for W in WIDTHS:
+        run_and_compare(Engine, S.crop_scene("batch", W), W, knobs, f"batch {W} {knobs}")
 
 
-def batch_frames():
-    f0 = np.full((H, W), PLANE, np.uint16)
-    f0[WAVE_ROWS[0]:WAVE_ROWS[1] + 1, WAVE0] = NEAR
-    f1 = np.full((H, W), PLANE, np.uint16)
-    f1[ZERO_ROW, :SEG] = 0
-    # a sawtooth of 0.3 m steps with period 5 (2.6 .. 3.8 m, inside the box): the left and right
-    # neighbours of every ring stand at different depths, no pixel finds a surface
-    f1[NOISE_ROW, :SEG] = (2600 + 300 * (np.arange(SEG) % 5)).astype(np.uint16)
-    f2 = np.full((H, W), PLANE, np.uint16)
-    f2[14:19, 40:90] = 0  # a hole, so that the last frame is not a copy of a plane
-    return [f0, f1, f2]
+@pytest.mark.parametrize("knobs", [POINTS, RUNS])
+def test_single_frames_of_the_batch_match_oracle(Engine, knobs):
+    """The batch's frames one at a time (no frame_pt_start: an empty first segment may leave)."""
+    for W in WIDTHS:
+        sc = S.crop_scene("batch", W)
+        run_and_compare(Engine, sc, W, knobs, f"frames {W} {knobs}",
+                        frames=[[f] for f in sc.frames], ref=[[r] for r in sc.ref])
 
 
-def run_oracle(frames_of_cams, p):
-    """Frame by frame through the oracle (one engine, the grid's history carried on): per frame
-    its results and stage masks, copied."""
-    orc = OracleFusion(threads=4)
-    out = []
-    for args in frames_of_cams:
-        orc.clear()
-        for a in args:
-            orc.addDepthmap(*a)
-        orc.processFrame(p)
-        st = orc.stage_arrays()
-        out.append({"points": orc.downloadPoints().copy(), "keys": orc.downloadVoxelCoords().copy(),
-                    "vox": orc.downloadVoxelizedPoints()[:, :3].copy(),
-                    "grid": orc.downloadVoxelOccupancyGrid().copy(),
-                    "hist": orc.historic_grid().copy(),
-                    "maskA": st["maskA"].copy() != 0, "maskB": st["maskB"].copy() != 0})
-    return out
+@pytest.mark.parametrize("knobs", [POINTS, RUNS])
+def test_crop_off_matches_oracle(Engine, knobs):
+    """Scene 6: a dense frame with the box at +-1e9 (everything the filter passes is kept)."""
+    for W in WIDTHS:
+        run_and_compare(Engine, S.crop_scene("nocrop", W), W, knobs, f"nocrop {W} {knobs}")
 
 
-@functools.lru_cache(maxsize=None)
-def scene(name):
-    """(params, per frame the cameras' addDepthmap arguments, the oracle's per-frame results)."""
-    if name == "batch":
-        cam = synth.make_camera(0, W, H)
-        p = box_params(*BATCH_BOX)
-        frames = [[cam_args(cam, d)] for d in batch_frames()]
-    elif name == "nocrop":
-        cam = synth.make_camera(0, W, H)
-        p = box_params((-1e9, -1e9, -1e9), (1e9, 1e9, 1e9))
-        frames = [[cam_args(cam, synth.dense_frame(cam, 0, 3))]]
-    elif name == "twocam":
-        # 16 rows: z of row v is 1 - 3 (v - 8) / 192; 0.95..1.06 keeps rows 5..11 of both cameras
-        cams = synth.cameras(2, W, 16)
-        p = box_params((-10.0, -20.0, 0.95), (30.0, 20.0, 1.06))
-        d = np.full((16, W), PLANE, np.uint16)
-        frames = [[cam_args(c, d) for c in cams]]
-    else:
-        raise KeyError(name)
-    ref = run_oracle(frames, p)
-    scene_contents(name, frames, ref)
-    return p, frames, ref
+@pytest.mark.parametrize("knobs", [POINTS, RUNS, {"GDF_NO_SEG_UNIFORM": "1"},
+                                   {"GDF_NO_SEG_UNIFORM": "1", **RUNS}])
+def test_two_cameras_match_oracle(Engine, knobs):
+    """Scene 7: two W x 16 cameras in one frame, the rows above and below the box empty; the
+    segment's camera by division (equal cameras) and by the lane ballot."""
+    for W in WIDTHS:
+        run_and_compare(Engine, S.crop_scene("twocam", W), W, knobs, f"twocam {W} {knobs}")
 
 
-def scene_contents(name, frames, ref):
-    """The cases the scenes must contain, asserted from the oracle's stage masks (maskB: after
-    the flying filter, maskA: after the crop) and the depth maps."""
-    if name == "nocrop":
-        r = ref[0]
-        assert np.array_equal(r["maskA"], r["maskB"]) and r["maskA"].any()  # 6: the crop is off
-        return
-    if name == "twocam":
-        r = ref[0]
-        A = r["maskA"].reshape(2, 16, W)
-        B = r["maskB"].reshape(2, 16, W)
-        for k in range(2):
-            assert A[k, 5:12].any() and not A[k, :5].any() and not A[k, 12:].any()
-            # 7: empty segments of both cameras that only the crop empties
-            assert B[k, 4, 4:SEG].all() and B[k, 4, SEG:W - 4].all()
-        return
-    depth = [f[0][0] for f in frames]
-    A = [r["maskA"].reshape(H, W) for r in ref]
-    B = [r["maskB"].reshape(H, W) for r in ref]
-    # 1: a mid-frame segment, every pixel valid, flying-clean (columns 4.. of the row's first
-    # segment), nothing kept
-    assert (depth[0][MID_ROW, :SEG] != 0).all()
-    assert B[0][MID_ROW, 4:SEG].all() and not A[0][MID_ROW, :SEG].any()
-    # 2: the first segment of frames 1 and 2, and the last segment of the last frame: valid
-    # depth, outside the box (the plane of their rows is cropped: their clean neighbours in the
-    # rows next to them are), nothing kept
-    for f in (1, 2):
-        assert (depth[f][0, :SEG] != 0).all() and not A[f][0, :SEG].any()
-        assert B[f][4, 4:SEG].all() and not A[f][:ROWS_KEPT[0]].any()
-    assert (depth[2][H - 1, SEG:] != 0).all() and not A[2][H - 1, SEG:].any()
-    assert B[2][H - 5, 4:W - 4].all() and not A[2][ROWS_KEPT[1] + 1:].any()
-    # 3: wave 0's 128 pixels valid and cropped, wave 1 keeps pixels, in one segment
-    y = (WAVE_ROWS[0] + WAVE_ROWS[1]) // 2
-    assert (depth[0][y, WAVE0] == NEAR).all() and not A[0][y, WAVE0].any()
-    assert B[0][y, WAVE0[8:56]].all() and B[0][y, WAVE0[72:120]].all()  # (clean away from steps)
-    assert A[0][y, WAVE1].sum() >= 64
-    # 4: kept pixels with a depth-valid neighbour outside the crop (flying-clean and not kept:
-    # the crop alone removed it) within 4 pixels in a row or a column
-    out = B[0] & ~A[0]
-    near = np.zeros((H, W), bool)
-    for i in range(1, 5):
-        near[i:, :] |= out[:-i, :]
-        near[:-i, :] |= out[i:, :]
-        near[:, i:] |= out[:, :-i]
-        near[:, :-i] |= out[:, i:]
-    assert np.count_nonzero(A[0] & near) >= 50
-    # 5: a segment without depth, and one with depth, inside the box, emptied by the filter
-    assert not depth[1][ZERO_ROW, :SEG].any() and not A[1][ZERO_ROW, :SEG].any()
-    d = depth[1][NOISE_ROW, :SEG].astype(np.float64) * 1e-3
-    z = 1.0 - (NOISE_ROW - H / 2) / (0.6 * W) * d
-    assert (d > 2.1).all() and (d < 5.9).all() and (z > 0.81).all() and (z < 1.09).all()
-    assert not B[1][NOISE_ROW, :SEG].any()
-    assert A[1][NOISE_ROW + 1, SEG:W - 4].all()  # (the rows around it still keep pixels)
-
-
-def run_gpu(gpu, p, frames):
+@pytest.mark.parametrize("nparts", [1, 3])
+def test_batch_through_the_emit_partition_matches_oracle(Engine, nparts):
+    """10: the 3-frame batch with the send lists of a key-range partition written by the
+    compaction itself (gdf_set_emit_partition: k_mask_px + k_emit_px2_parts<256>); every part
+    voxelized on its own equals the oracle's voxel means and marks of each frame
+    (test_gpu_round4.py::test_partition_runs_voxelize_runs_match_oracle's method)."""
+    from ros_gpu_depthmap_fusion_amd import hiprt
+    p, frames, ref = S.crop_scene("batch", 448)
+    B = len(frames)
+    gpu = engine_with(Engine, **S.PX_ENV)
     gpu.clear()
     for j, args in enumerate(frames):
         if j:
             gpu.nextFrameInBatch()
         for a in args:
             gpu.addDepthmap(*a)
-    gpu.processFrame(p)
-
-
-def compare_frames(gpu, ref, tag):
-    """Every frame of the batch the engine just ran against the oracle's frame: points, voxel
-    keys, voxel means and grid bit for bit, and batch_ranges consistent with them."""
-    pts, keys, vox = gpu.downloadPoints(), gpu.downloadVoxelCoords(), gpu.downloadVoxelizedPoints()
-    B = len(ref)
-    if B == 1:
-        ps, vs = [0, len(pts)], [0, len(vox)]
-    else:
-        ps, vs = gpu.batch_ranges()
-        assert len(ps) == B + 1 and len(vs) == B + 1, tag
-        assert ps[0] == 0 and vs[0] == 0 and ps[B] == len(pts) and vs[B] == len(vox), tag
-    for j, r in enumerate(ref):
-        assert ps[j + 1] - ps[j] == len(r["points"]), (tag, j, ps[j + 1] - ps[j], len(r["points"]))
-        assert vs[j + 1] - vs[j] == len(r["vox"]), (tag, j)
-        assert np.array_equal(pts[ps[j]:ps[j + 1]].view(np.uint32), r["points"].view(np.uint32)), (tag, j)
-        assert np.array_equal(keys[ps[j]:ps[j + 1]], r["keys"]), (tag, j)
-        assert np.array_equal(vox[vs[j]:vs[j + 1], :3].view(np.uint32), r["vox"].view(np.uint32)), (tag, j)
-        grid = gpu.downloadBatchVoxelOccupancyGrid(j) if B > 1 else gpu.downloadVoxelOccupancyGrid()
-        assert np.array_equal(grid, r["grid"]), (tag, j)
-    assert np.array_equal(gpu.downloadVoxelOccupancyGrid(), ref[-1]["grid"]), tag
-    assert np.array_equal(gpu.historic_grid(), ref[-1]["hist"]), tag
-
-
-RUNS, POINTS = {"GDF_FORCE_RUNS": "1"}, {}
-
-
-@pytest.mark.parametrize("knobs", [POINTS, RUNS, {"GDF_NO_MASK_PACKED": "1"},
-                                   {"GDF_NO_MASK_PACKED": "1", **RUNS}])
-def test_batch_of_cropped_segments_matches_oracle(Engine, knobs):
-    """Scenes 1-5 in one 3-frame batch of 320 x 32 frames (8, 9: run and points mode, the packed
-    and the scalar px form)."""
-    p, frames, ref = scene("batch")
-    gpu = engine_with(Engine, **knobs)
-    run_gpu(gpu, p, frames)
-    compare_frames(gpu, ref, f"batch {knobs}")
-
-
-@pytest.mark.parametrize("knobs", [POINTS, RUNS])
-def test_single_frames_of_the_batch_match_oracle(Engine, knobs):
-    """The batch's frames one at a time (no frame_pt_start: an empty first segment may leave)."""
-    p, frames, ref = scene("batch")
-    gpu = engine_with(Engine, **knobs)
-    for j, args in enumerate(frames):
-        run_gpu(gpu, p, [args])
-        compare_frames(gpu, [ref[j]], f"frame {j} {knobs}")
-
-
-@pytest.mark.parametrize("knobs", [POINTS, RUNS])
-def test_crop_off_matches_oracle(Engine, knobs):
-    """Scene 6: a dense frame with the box at +-1e9 (everything the filter passes is kept)."""
-    p, frames, ref = scene("nocrop")
-    gpu = engine_with(Engine, **knobs)
-    run_gpu(gpu, p, frames)
-    compare_frames(gpu, ref, f"nocrop {knobs}")
-
-
-@pytest.mark.parametrize("knobs", [POINTS, RUNS, {"GDF_NO_SEG_UNIFORM": "1"},
-                                   {"GDF_NO_SEG_UNIFORM": "1", **RUNS}])
-def test_two_cameras_match_oracle(Engine, knobs):
-    """Scene 7: two 320 x 16 cameras in one frame, the rows above and below the box empty; the
-    segment's camera by division (equal cameras) and by the lane ballot."""
-    p, frames, ref = scene("twocam")
-    gpu = engine_with(Engine, **knobs)
-    run_gpu(gpu, p, frames)
-    compare_frames(gpu, ref, f"twocam {knobs}")
+    cap = 448 * S.CROP_H * B  # (the send buffers hold the frames' pixels before compaction)
+    sp, srk, srs = hiprt.DeviceArray(16 * cap), hiprt.DeviceArray(4 * cap), hiprt.DeviceArray(4 * cap)
+    cnt = hiprt.DeviceArray(8 * nparts)
+    gpu.set_emit_partition(nparts, sp.ptr, srk.ptr, srs.ptr, cap, cnt.ptr)
+    gpu.processFrame(p, synchronous=True, defer_occupancy_grid=True, defer_voxelize=True)
+    assert gpu.frame_kernels() == {"mask": S.K_MASK_O8, "emit": S.K_EMIT_PARTS}, gpu.frame_kernels()
+    gpu.synchronize()
+    voxelize_parts_and_compare(gpu, nparts, B, sp, srk, srs, cnt, [r["vox"] for r in ref],
+                               [r["keys"] for r in ref], ("crop-first batch", nparts))
 
 
 def test_debug_stage_masks_at_launch_defaults(Engine):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from drive import compare_results
+from drive import compare_results, voxelize_parts_and_compare
 from oracle import OracleFusion
 from ros_gpu_depthmap_fusion_amd import synth
 from ros_gpu_depthmap_fusion_amd.gdf import ComponentParams
@@ -201,7 +201,7 @@ def test_partition_runs_voxelize_runs_match_oracle(Engine, nparts, B, emit):
     the same send lists from gdf_set_emit_partition (the compaction writes them: k_mask_px +
     k_emit_px2 on the 256-pixel segments of frames over 1 Mi pixels; a single VGA frame takes the
     compaction + partition pass)."""
-    from ros_gpu_depthmap_fusion_amd import hiprt, multi
+    from ros_gpu_depthmap_fusion_amd import hiprt
     p = ComponentParams()
     cam = synth.make_camera(0, 640, 480)
     gpu, orc = Engine(), OracleFusion(threads=16)
@@ -220,63 +220,14 @@ def test_partition_runs_voxelize_runs_match_oracle(Engine, nparts, B, emit):
     if not emit:
         gpu.partition_runs(nparts, sp.ptr, srk.ptr, srs.ptr, cap, cnt.ptr)
     gpu.synchronize()
-    c = cnt.to_numpy(np.uint32, 2 * nparts)
-    pts, runs = c[:nparts].astype(np.int64), c[nparts:].astype(np.int64)
-    n = int(pts.sum())
-    assert (runs <= pts).all() and ((runs > 0) == (pts > 0)).all()
-    P0, R0 = np.concatenate([[0], np.cumsum(pts)]), np.concatenate([[0], np.cumsum(runs)])
-    h_rs = srs.to_numpy(np.uint32, max(n, 1))
-    # every part's voxel marks (gdf_voxelize_runs_marked): frame j at j * stride words; part q's
-    # keys are whole mark words [q S, (q + 1) S) (the fused step all-gathers those slices)
-    ncells = int(gpu.grid_size()[1])
-    words = (ncells + 31) // 32
-    S = multi.part_slice_words(nparts, ncells)
-    stride = S * nparts
-    union = np.zeros((B, stride), np.uint32)
-    want, want_marks = [], np.zeros((B, words), np.uint32)
+    want, want_keys = [], []
     for j in range(B):
         orc.clear()
         orc.addDepthmap(*cam_args(cam, frames[j]))
         orc.processFrame(p)
         want.append(orc.downloadVoxelizedPoints()[:, :3])
-        k = np.unique(orc.downloadVoxelCoords().astype(np.int64))
-        np.bitwise_or.at(want_marks[j], k >> 5, (np.uint32(1) << (k & 31).astype(np.uint32)))
-    got = [[] for _ in range(B)]
-    for q in range(nparts):
-        if pts[q] == 0:
-            continue
-        rs = h_rs[R0[q]:R0[q + 1]]
-        assert rs[0] == 0 and (np.diff(rs.astype(np.int64)) > 0).all() and rs[-1] < pts[q]
-        # the part as two sources split at a run boundary (a key range from two ranks)
-        cut = len(rs) // 2
-        pb = np.array([0, rs[cut], pts[q]] if cut else [0, pts[q]], np.uint32)
-        rb = np.array([0, cut, len(rs)] if cut else [0, len(rs)], np.uint32)
-        local = rs.astype(np.uint32).copy()
-        if cut:
-            local[cut:] -= rs[cut]
-        drs = hiprt.DeviceArray.from_numpy(np.concatenate([local, np.zeros(1, np.uint32)]))
-        dmk = hiprt.DeviceArray.from_numpy(np.zeros(B * stride, np.uint32))
-        gpu.voxelize_runs_marked(sp.ptr + 16 * int(P0[q]), srk.ptr + 4 * int(R0[q]), drs.ptr, pb, rb,
-                                 dmk.ptr, stride)
-        gpu.synchronize()
-        mk = dmk.to_numpy(np.uint32, B * stride).reshape(B, stride)
-        outside = np.ones(stride, bool)
-        outside[q * S:(q + 1) * S] = False
-        assert not mk[:, outside].any(), (nparts, B, q)
-        union |= mk
-        vox = gpu.downloadVoxelizedPoints()[:, :3]
-        if B > 1:
-            _, vs = gpu.batch_ranges()
-            for j in range(B):
-                got[j].append(vox[vs[j]:vs[j + 1]])
-        else:
-            got[0].append(vox)
-    for j in range(B):
-        g = np.concatenate(got[j]) if got[j] else np.zeros((0, 3), np.float32)
-        assert len(g) == len(want[j]) > 0, (nparts, B, j)
-        assert np.array_equal(g.view(np.uint32), want[j].view(np.uint32)), (nparts, B, j)
-        assert np.array_equal(union[j, :words], want_marks[j]), (nparts, B, j)
-        assert not union[j, words:].any()
+        want_keys.append(orc.downloadVoxelCoords())
+    voxelize_parts_and_compare(gpu, nparts, B, sp, srk, srs, cnt, want, want_keys, (nparts, B))
 
 
 def test_tuning_is_a_snapshot_per_engine(Engine):
