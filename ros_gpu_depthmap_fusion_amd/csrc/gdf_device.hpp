@@ -105,9 +105,10 @@ static_assert(sizeof(CamDesc) % 16 == 0, "CamDesc must stay 16-byte sized");
 
 // Launch-shape choices of one engine (host-side; the kernels never read it).  None changes a
 // result: each alternative is parity-tested against the oracle (test_gpu_round3/4/5).  An engine
-// takes its snapshot at gdf_create - a GDF_* variable when set, the default otherwise - and its
-// launches read only that snapshot, so engines created under other environments (other threads,
-// the in-process world's ranks) never retune it; gdf_create logs every value that differs from
+// takes its snapshot at gdf_create (gdf_engine.cpp's knob table: a GDF_* variable when set, the
+// default here otherwise) and its launches read only that snapshot, so engines created under
+// other environments (other threads, the in-process world's ranks) never retune it; gdf_create
+// logs every value that differs from
 // its default.
 struct Tuning {
     uint32_t mask_px2 = 2;            // GDF_MASK_PX: pixels per k_mask thread (2, or 1: k_mask)
@@ -122,9 +123,7 @@ struct Tuning {
     uint32_t run_inblock = 1024;      // GDF_RUN_INBLOCK: in-block group size limit
     uint32_t run_wave = 2;            // GDF_RUN_WAVE: staged long groups 0 queued, 1 a wave, 2 4 lanes
     uint32_t small_group = 32;        // GDF_SMALL_GROUP: thread-summed group size
-    uint32_t points_lane = 0;         // GDF_POINTS_LANE: k_group's long staged groups by 4-lane chains
     uint32_t run_wave_mode = 1;       // GDF_RUN_WAVE_MODE: queued groups 0 block, 1 by queue, 2 wave
-    uint32_t run_big_occ4 = 0;        // GDF_RUN_BIG_OCC4: k_group_runs_big at 4 waves per SIMD
     uint32_t run_big_blocks = 1024;   // GDF_RUN_BIG_BLOCKS: k_group_runs_big grid cap
     uint32_t run_q16 = 2;             // GDF_RUN_Q16: chunks of 1 K points 0 never, 1 always, 2 single frames
 };

@@ -304,19 +304,6 @@ enum MiscSlot {
 }  // namespace
 
 
-// every environment variable that selects a launch shape or an alternative form (none changes a
-// result: DESIGN.md §5 "Tuning knobs"); read at gdf_create only
-constexpr const char* kTuningVars[] = {
-    "GDF_MASK_PX", "GDF_MASK_OCC8", "GDF_EMIT_PX2", "GDF_GRID_WPT", "GDF_SORT_BLOCKS",
-    "GDF_GROUP_BLOCKS", "GDF_GROUP_SCAN_TILES", "GDF_GROUP_FIRST", "GDF_RUN_STAGE",
-    "GDF_RUN_INBLOCK", "GDF_RUN_WAVE", "GDF_SMALL_GROUP", "GDF_POINTS_LANE", "GDF_RUN_WAVE_MODE",
-    "GDF_RUN_BIG_OCC4", "GDF_RUN_BIG_BLOCKS", "GDF_RUN_Q16", "GDF_SORT_PT", "GDF_SEG_ITEMS",
-    "GDF_SEL_SHAPE", "GDF_H2D_THREADS", "GDF_NO_GRAPHS", "GDF_NO_RUNS", "GDF_FORCE_RUNS",
-    "GDF_RUN_HIST_SORT", "GDF_RUN_HIST_ALL", "GDF_NO_PACK_RUNS", "GDF_NO_XRUNS",
-    "GDF_NO_GROUP_SCAN", "GDF_NO_MASK_PACKED", "GDF_NO_GRID_DELTA", "GDF_NO_EMIT_PART",
-    "GDF_NO_DL_PREFETCH", "GDF_DL_FORK", "GDF_GRID_GATE", "GDF_NO_SEL_KEY_LDS",
-    "GDF_NO_SEG_UNIFORM"};
-
 constexpr int kMaxPipe = 4;
 // batches of frames of at most this many depth pixels each run k_group_runs_big on this many blocks
 constexpr uint64_t kSmallFramePixels = 640 * 480;
@@ -397,8 +384,6 @@ struct Slot {
     bool pf_valid = false;          // this slot's last frame wrote its downloads (k_download)
     bool sel_frame = false;         // this slot's last frame compacted rollbuffer points (k_sel)
     bool part_emitted = false;      // this slot's last compaction wrote the emit partition
-    hipStream_t dl_aux = nullptr;   // k_download of the points / coords, after the compaction,
-    hipEvent_t dl_ev = nullptr;     // overlapping the voxelize (an event after the compaction)
     DevBuf d_didx, d_ddata;         // the grid delta of this slot's single-frame update
     bool delta_valid = false;
     uint32_t delta_ticket = 0;      // ... and that update's sequence number
@@ -522,32 +507,34 @@ struct gdf_engine {
     int rot45 = 0;
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
 
-    Tuning tune;                    // launch shapes, a snapshot at gdf_create
+    // The engine's snapshot of the GDF_* tuning variables, taken once at gdf_create (kKnobs below:
+    // the one place that reads them): Tuning, and the switches and shapes among the members here
+    // whose comment names a variable.  Each holds its default until read_knobs finds it set.
+    Tuning tune;                    // launch shapes
     std::string tuning_set;         // the GDF_* tuning variables set at creation ("K=V K=V")
     // the last depth compaction's kernels, null without one (gdf_get_frame_kernels)
     const void *frame_mask = nullptr, *frame_emit = nullptr;
-    int sort_pt = 0;  // radix keys per thread (4, 8, 16); 0: chosen by frame capacity
-    uint32_t sel_segs = kSelSegs, sel_threads = kSelThreads;  // k_sel tile shape
+    int sort_pt = 0;  // GDF_SORT_PT: radix keys per thread (4, 8, 16); 0: chosen by frame capacity
+    uint32_t sel_segs = kSelSegs, sel_threads = kSelThreads;  // GDF_SEL_SHAPE: k_sel tile shape
     bool sel_shape_set = false;     // GDF_SEL_SHAPE given (else the shape follows the window)
-    uint32_t seg_items = 0;  // max pixels per depth compaction segment (64..1024); 0: by frame size
-    bool use_graphs = !getenv("GDF_NO_GRAPHS");  // gdf_set_graphs
-    bool use_runs = !getenv("GDF_NO_RUNS");      // voxelize runs of equal keys (depth frames)
-    bool force_runs = getenv("GDF_FORCE_RUNS") != nullptr;    // tuning knob: runs at every size
-    bool run_hist_in_sort = getenv("GDF_RUN_HIST_SORT") != nullptr;  // tuning knob
+    uint32_t seg_items = 0;  // GDF_SEG_ITEMS: max pixels per depth compaction segment (64..1024); 0: by frame size
+    bool use_graphs = true;         // GDF_NO_GRAPHS, gdf_set_graphs
+    bool use_runs = true;           // GDF_NO_RUNS: voxelize runs of equal keys (depth frames)
+    bool force_runs = false;        // GDF_FORCE_RUNS: runs at every size
+    bool run_hist_in_sort = false;  // GDF_RUN_HIST_SORT
     // the runs' lengths packed into the sort keys, their first points as the sorted values (the
     // group phase reads no run_start[index] gathers); GDF_NO_PACK_RUNS: the index form
-    bool pack_runs = !getenv("GDF_NO_PACK_RUNS");
-    bool run_hist_all = getenv("GDF_RUN_HIST_ALL") != nullptr;  // tuning knob: k_mask counts the
-                                                               // run digits at any segment count
-    bool xruns = !getenv("GDF_NO_XRUNS");  // voxelize_points sorts the received list's runs
-    bool group_scan = !getenv("GDF_NO_GROUP_SCAN");  // segment offsets without scan launches
-    bool mask_packed = !getenv("GDF_NO_MASK_PACKED");  // k_mask_px<2>: packed f32 pixel pairs
-    bool sel_key_lds = !getenv("GDF_NO_SEL_KEY_LDS");  // k_sel: the keys kept in LDS (A/B)
-    bool seg_uniform = !getenv("GDF_NO_SEG_UNIFORM");  // equal cameras: segment -> camera by division
+    bool pack_runs = true;
+    bool run_hist_all = false;  // GDF_RUN_HIST_ALL: k_mask counts the run digits at any segment count
+    bool xruns = true;          // GDF_NO_XRUNS: voxelize_points sorts the received list's runs
+    bool group_scan = true;     // GDF_NO_GROUP_SCAN: segment offsets without scan launches
+    bool mask_packed = true;    // GDF_NO_MASK_PACKED: k_mask_px<2>: packed f32 pixel pairs
+    bool sel_key_lds = true;    // GDF_NO_SEL_KEY_LDS: k_sel: the keys kept in LDS (A/B)
+    bool seg_uniform = true;    // GDF_NO_SEG_UNIFORM: equal cameras: segment -> camera by division
     // host mirror of the u8 grid (gdf_download_frame): after the first grid download, single-frame
     // updates also list the 32-cell groups they changed, and the next download moves only those
     bool grid_delta = false;
-    bool grid_delta_allowed = !getenv("GDF_NO_GRID_DELTA");
+    bool grid_delta_allowed = true;  // GDF_NO_GRID_DELTA
     Slot::Pinned h_mirror;
     // after a single-frame gdf_download_frame of points / coords / voxels: single frames end with
     // k_download into the slot's pinned mirrors (the next download_frame waits once)
@@ -559,14 +546,11 @@ struct gdf_engine {
         uint32_t *run_keys = nullptr, *run_starts = nullptr, *counts = nullptr;
         uint32_t nseg = 1;  // gdf_set_partition_segments: [depth | rollbuffer pieces] buckets
     } epart;
-    bool emit_part = !getenv("GDF_NO_EMIT_PART");  // (else: compaction, then the partition pass)
+    bool emit_part = true;  // GDF_NO_EMIT_PART (else: compaction, then the partition pass)
     // a frame armed with gdf_set_emit_partition sets its occupancy marks (gdf_set_partition_marks:
     // off when the caller builds the union from the key-range voxelize, gdf_voxelize_runs_marked)
     bool part_marks = true;
-    bool dl_prefetch_allowed = !getenv("GDF_NO_DL_PREFETCH");
-    // tuning knob GDF_DL_FORK: the points / coords part on a second stream right after the
-    // compaction (direct launches) instead of in the chain's last kernel (graph replays)
-    bool dl_fork = getenv("GDF_DL_FORK") != nullptr;
+    bool dl_prefetch_allowed = true;  // GDF_NO_DL_PREFETCH
     bool mirror_valid = false;
     uint32_t mirror_ticket = 0, mirror_gen = 0;
 
@@ -589,17 +573,8 @@ struct gdf_engine {
     // the waiter in any hardware queue the two share (in-order dispatch) - and the waiters of at
     // most 4 slots (<= 4 x ~205 blocks of one wave each) leave the chip's other ~7 K wave slots to
     // it; kSpinLimit turns a stall into GDF_ERR_DEVICE regardless.
-    // GDF_GRID_GATE=1 orders direct launches by the streams as well: a launch carrying an update
-    // waits for the event recorded after the previous update when that one ran on another stream
-    // (GDF_GRID_GATE=early: recorded right before it - next in its stream, dispatchable), so no
-    // block ever waits for work queued on another stream.  Measured on MI355X (A/B, one box, 2000
-    // steps each, profiles/r06/grid_gate/): C2 30.2 (tickets) vs 28.7 (gate) / 28.9 (early) -
-    // each cross-stream wait costs the batch's chain more than the spin it removes.
-    const char* grid_gate_env = getenv("GDF_GRID_GATE");
-    bool grid_gate = grid_gate_env != nullptr;
-    bool grid_gate_early = grid_gate_env && std::strcmp(grid_gate_env, "early") == 0;
-    hipEvent_t grid_ev = nullptr;       // recorded after the last gated update
-    hipStream_t grid_ev_stream = nullptr;  // ... on this stream (nullptr: none yet)
+    // (A stream gate that also ordered the updates by events between the streams was measured
+    // at -5 % on the C2 line and removed.)
     uint32_t grid_gen = 0;          // bumped when the grid is (re)allocated: slots re-zero marks
     int grid_mode = 0;  // 0: u8 grid = history (lifetime <= 255); 1: u32 history + u8 output
     bool grid_alloc = false;
@@ -711,27 +686,100 @@ struct gdf_engine {
         q.err = sl().d_misc.as<uint32_t>() + kErr;
         return q;
     }
-    // the stream gate of a grid update launched on st: the event to wait for before it (null:
-    // none - the previous gated update ran on st, or there was none) and the one to record after
-    hipEvent_t grid_gate_wait(hipStream_t st) const {
-        return grid_gate && npipe > 1 && grid_ev_stream && grid_ev_stream != st ? grid_ev : nullptr;
-    }
-    hipEvent_t grid_gate_record(hipStream_t st) {
-        if (!grid_gate || npipe <= 1) return nullptr;
-        if (!grid_ev) HIPCHK(hipEventCreateWithFlags(&grid_ev, hipEventDisableTiming));
-        grid_ev_stream = st;
-        return grid_ev;
-    }
-    // a grid-update launch of its own on st, between the gate's wait and record
-    template <class F>
-    void grid_gated(hipStream_t st, F&& launch) {
-        if (hipEvent_t w = grid_gate_wait(st)) HIPCHK(hipStreamWaitEvent(st, w, 0));
-        launch();
-        if (hipEvent_t r = grid_gate_record(st)) HIPCHK(hipEventRecord(r, st));
-    }
 };
 
 namespace {
+
+// Every GDF_* variable that selects a launch shape or an alternative form (none changes a result:
+// DESIGN.md §5 "Tuning knobs"), one row each, in the order gdf_get_tuning reports them.  A field
+// keeps the default of its declaration (Tuning, gdf_engine) unless its variable is set:
+//   kInt    the value, clamped to [lo, hi], into a Tuning field
+//   kOn     set (to anything): the switch is true          kOff    set: the switch is false
+//   kParse  a parser of its own (an invalid value leaves the default)
+//   kNamed  read where it is used, listed here only so that it is reported
+struct Knob {
+    enum Kind { kInt, kOn, kOff, kParse, kNamed };
+    const char* name;
+    Kind kind;
+    uint32_t Tuning::*value;
+    int lo, hi;
+    bool gdf_engine::*flag;
+    void (*parse)(gdf_engine*, const char*);
+};
+constexpr Knob knob_int(const char* n, uint32_t Tuning::*f, int lo = 0, int hi = INT32_MAX) {
+    return {n, Knob::kInt, f, lo, hi, nullptr, nullptr};
+}
+constexpr Knob knob_on(const char* n, bool gdf_engine::*f) { return {n, Knob::kOn, nullptr, 0, 0, f, nullptr}; }
+constexpr Knob knob_off(const char* n, bool gdf_engine::*f) { return {n, Knob::kOff, nullptr, 0, 0, f, nullptr}; }
+constexpr Knob knob_parse(const char* n, void (*p)(gdf_engine*, const char*)) {
+    return {n, Knob::kParse, nullptr, 0, 0, nullptr, p};
+}
+constexpr Knob knob_named(const char* n) { return {n, Knob::kNamed, nullptr, 0, 0, nullptr, nullptr}; }
+
+const Knob kKnobs[] = {
+    knob_int("GDF_MASK_PX", &Tuning::mask_px2),
+    knob_int("GDF_MASK_OCC8", &Tuning::mask_occ8),
+    knob_int("GDF_EMIT_PX2", &Tuning::emit_px2),
+    knob_int("GDF_GRID_WPT", &Tuning::grid_wpt, 1, 8),
+    knob_int("GDF_SORT_BLOCKS", &Tuning::sort_blocks, 1),
+    knob_int("GDF_GROUP_BLOCKS", &Tuning::group_blocks, 1),
+    knob_int("GDF_GROUP_SCAN_TILES", &Tuning::group_scan_tiles, 1),
+    knob_int("GDF_GROUP_FIRST", &Tuning::group_first),
+    knob_int("GDF_RUN_STAGE", &Tuning::run_stage, 1),  // 512 or 2048
+    knob_int("GDF_RUN_INBLOCK", &Tuning::run_inblock),
+    knob_int("GDF_RUN_WAVE", &Tuning::run_wave),
+    knob_int("GDF_SMALL_GROUP", &Tuning::small_group),
+    knob_int("GDF_RUN_WAVE_MODE", &Tuning::run_wave_mode),
+    knob_int("GDF_RUN_BIG_BLOCKS", &Tuning::run_big_blocks, 1),
+    knob_int("GDF_RUN_Q16", &Tuning::run_q16),
+    knob_parse("GDF_SORT_PT", [](gdf_engine* e, const char* v) { e->sort_pt = std::atoi(v); }),
+    knob_parse("GDF_SEG_ITEMS", [](gdf_engine* e, const char* v) {
+        const uint32_t si = (uint32_t)std::atoi(v);
+        if (si >= 64 && si <= kSegItems && si % 64 == 0) e->seg_items = si;
+    }),
+    knob_parse("GDF_SEL_SHAPE", [](gdf_engine* e, const char* v) {  // "segs,threads"
+        unsigned sg = 0, th = 0;
+        if (std::sscanf(v, "%u,%u", &sg, &th) == 2 && (sg == 4 || sg == 8 || sg == 16) &&
+            th >= 128 && th <= 1024 && th % 64 == 0 && sg * (th / 64) <= 256) {
+            e->sel_segs = sg;
+            e->sel_threads = th;
+            e->sel_shape_set = true;
+        }
+    }),
+    knob_named("GDF_H2D_THREADS"),  // (the staging copier's threads())
+    knob_off("GDF_NO_GRAPHS", &gdf_engine::use_graphs),
+    knob_off("GDF_NO_RUNS", &gdf_engine::use_runs),
+    knob_on("GDF_FORCE_RUNS", &gdf_engine::force_runs),
+    knob_on("GDF_RUN_HIST_SORT", &gdf_engine::run_hist_in_sort),
+    knob_on("GDF_RUN_HIST_ALL", &gdf_engine::run_hist_all),
+    knob_off("GDF_NO_PACK_RUNS", &gdf_engine::pack_runs),
+    knob_off("GDF_NO_XRUNS", &gdf_engine::xruns),
+    knob_off("GDF_NO_GROUP_SCAN", &gdf_engine::group_scan),
+    knob_off("GDF_NO_MASK_PACKED", &gdf_engine::mask_packed),
+    knob_off("GDF_NO_GRID_DELTA", &gdf_engine::grid_delta_allowed),
+    knob_off("GDF_NO_EMIT_PART", &gdf_engine::emit_part),
+    knob_off("GDF_NO_DL_PREFETCH", &gdf_engine::dl_prefetch_allowed),
+    knob_off("GDF_NO_SEL_KEY_LDS", &gdf_engine::sel_key_lds),
+    knob_off("GDF_NO_SEG_UNIFORM", &gdf_engine::seg_uniform),
+};
+
+// gdf_create: the engine's snapshot of the table's variables, and their names and values as set
+// ("K=V K=V": logged once, kept for gdf_get_tuning - a stray one must not switch kernels silently)
+void read_knobs(gdf_engine* e) {
+    for (const Knob& k : kKnobs) {
+        const char* v = std::getenv(k.name);
+        if (!v) continue;
+        switch (k.kind) {
+            case Knob::kInt: e->tune.*k.value = (uint32_t)std::min(k.hi, std::max(k.lo, std::atoi(v))); break;
+            case Knob::kOn: e->*k.flag = true; break;
+            case Knob::kOff: e->*k.flag = false; break;
+            case Knob::kParse: k.parse(e, v); break;
+            case Knob::kNamed: break;
+        }
+        e->tuning_set += std::string(k.name) + "=" + v + " ";
+    }
+    if (!e->tuning_set.empty()) e->tuning_set.pop_back();
+}
 
 void create_slot(Slot& sl) {
     if (sl.own) return;
@@ -1356,10 +1404,8 @@ void widen_if_needed(gdf_engine* e, uint32_t lifetime, hipStream_t st) {
     ensure_misc(e);
     e->d_hist32.ensure((size_t)e->ncells * 4);
     e->d_out8.ensure((size_t)((e->ncells + 31) / 32) * 32);
-    e->grid_gated(st, [&] {
-        HIPCHK(launch_widen_grid(e->d_grid8.as<uint8_t>(), e->d_hist32.as<uint32_t>(), e->ncells,
-                                 e->grid_seq(e->grid_ticket++), st));
-    });
+    HIPCHK(launch_widen_grid(e->d_grid8.as<uint8_t>(), e->d_hist32.as<uint32_t>(), e->ncells,
+                             e->grid_seq(e->grid_ticket++), st));
     e->grid_mode = 1;
 }
 
@@ -1798,19 +1844,9 @@ void voxelize_launched(gdf_engine* e, int fused_grid_lifetime) {
     e->sl().vox_valid = true;
 }
 
-// the stream gate of the grid update a direct voxelize launch carries (its first radix pass)
-VoxelizeArgs gated(gdf_engine* e, VoxelizeArgs v, hipStream_t st) {
-    if (v.grid8) {
-        v.grid_wait = e->grid_gate_wait(st);
-        v.grid_rec = e->grid_gate_record(st);
-        v.grid_rec_early = e->grid_gate_early ? 1 : 0;
-    }
-    return v;
-}
-
 void voxelize(gdf_engine* e, int average, int fused_grid_lifetime = -1) {
     e->sl().pf_valid = false;
-    const VoxelizeArgs v = gated(e, voxelize_args(e, average, fused_grid_lifetime), e->s());
+    const VoxelizeArgs v = voxelize_args(e, average, fused_grid_lifetime);
     e->timed(GDF_KERNEL_VOXELIZE, [&] { HIPCHK(launch_voxelize(v, e->s(), e->hook_ptr())); });
     voxelize_launched(e, fused_grid_lifetime);
 }
@@ -1835,23 +1871,13 @@ bool same_key(const FrameArgs& a, const VoxelizeArgs& v, const FrameArgs& ka, co
 // gdf_download_frame prefetch: a single frame's downloads written by k_download at the end of
 // its launch chain (after the voxelize and the grid update it carries)
 bool prefetch_on(const gdf_engine* e) { return e->dl_prefetch && e->nframes == 1 && !e->user_stream; }
-bool prefetch_fork(const gdf_engine* e) { return prefetch_on(e) && e->dl_fork; }
 
-// parts: DL_POINTS on the slot's aux stream right after the compaction (overlaps the voxelize),
-// the rest at the end of the chain
+// (at the end of the chain: the points part on a second stream right after the compaction
+// overlapped the voxelize but lost)
 void prefetch_downloads(gdf_engine* e, hipStream_t st, uint32_t parts) {
     Slot& q = e->sl();
     if (parts & DL_MISC) q.pf_valid = false;
     if (!prefetch_on(e)) return;
-    if (parts == DL_POINTS) {  // (forked: its own stream after the compaction)
-        if (!q.dl_aux) {
-            HIPCHK(hipStreamCreateWithFlags(&q.dl_aux, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&q.dl_ev, hipEventDisableTiming));
-        }
-        HIPCHK(hipEventRecord(q.dl_ev, st));
-        HIPCHK(hipStreamWaitEvent(q.dl_aux, q.dl_ev, 0));
-        st = q.dl_aux;
-    }
     const uint32_t cap = std::max<uint32_t>(q.n_total, 1);
     const uint32_t dcap = q.delta_valid ? (uint32_t)((mark_words(e) + 3) / 4 * 4) : 0u;
     const int set = q.mir_next();  // (never the set the caller holds)
@@ -1859,10 +1885,8 @@ void prefetch_downloads(gdf_engine* e, hipStream_t st, uint32_t parts) {
     // a mirror about to grow is freed first: no earlier k_download may still write it
     if (M.pts.bytes < (size_t)cap * 16 || M.coords.bytes < (size_t)cap * 4 ||
         M.vox.bytes < (size_t)cap * 16 || M.delta.bytes < (size_t)std::max<uint32_t>(dcap, 4) * 36 ||
-        M.misc.bytes < kMiscWords * 4) {
+        M.misc.bytes < kMiscWords * 4)
         HIPCHK(hipStreamSynchronize(q.stream()));
-        if (q.dl_aux) HIPCHK(hipStreamSynchronize(q.dl_aux));
-    }
     DlArgs d{};
     d.misc = q.d_misc.as<uint32_t>();
     d.misc_words = kMiscWords;
@@ -1908,11 +1932,10 @@ void run_fused_frame(gdf_engine* e, int average, uint32_t lifetime) {
         occupancy_grid(e, lifetime, e->s());
         return;
     }
-    // (a prefetching frame forks its points download after the compaction: direct launches)
     // (single frames only: a multi-frame batch launches directly - its replays measured 26.8 ->
     // 25.9 Gpoints/s on the C2 line once 8 descriptors fit the argument table)
     const bool eligible = e->use_graphs && !e->profiling && !e->debug && a.ncams <= kArgCams &&
-                          !e->user_stream && a.total_segs && !prefetch_fork(e) && e->nframes == 1;
+                          !e->user_stream && a.total_segs && e->nframes == 1;
     hipStream_t st = e->s();
     Slot::GraphEntry* hit = nullptr;
     if (eligible)
@@ -1993,12 +2016,10 @@ void run_fused_frame(gdf_engine* e, int average, uint32_t lifetime) {
         }
         if (e->profiling) e->timed(GDF_KERNEL_EVENT_FLOOR, [] {});
         e->timed(GDF_KERNEL_FRAME, [&] { HIPCHK(launch_frame(a, st, e->hook_ptr())); });
-        if (prefetch_fork(e)) prefetch_downloads(e, st, DL_POINTS);
-        const VoxelizeArgs vg = gated(e, v, st);
-        e->timed(GDF_KERNEL_VOXELIZE, [&] { HIPCHK(launch_voxelize(vg, st, e->hook_ptr())); });
+        e->timed(GDF_KERNEL_VOXELIZE, [&] { HIPCHK(launch_voxelize(v, st, e->hook_ptr())); });
     }
     voxelize_launched(e, (int)lifetime);
-    prefetch_downloads(e, st, DL_MISC | DL_VOX | DL_DELTA | (prefetch_fork(e) ? 0u : DL_POINTS));
+    prefetch_downloads(e, st, DL_MISC | DL_VOX | DL_DELTA | DL_POINTS);
 }
 
 void occupancy_grid(gdf_engine* e, uint32_t lifetime, hipStream_t st) {  // fusion.cpp:1757-1823
@@ -2014,14 +2035,12 @@ void occupancy_grid(gdf_engine* e, uint32_t lifetime, hipStream_t st) {  // fusi
     GridSeq q = e->grid_seq(e->grid_ticket);
     delta_args(e, q, e->grid_ticket, st == e->s());
     e->grid_ticket++;
-    e->grid_gated(st, [&] {
-        e->timed_on(GDF_KERNEL_GRID, st, [&] {
-            if (e->grid_mode == 0)
-                HIPCHK(launch_grid_u8(e->d_grid8.as<uint8_t>(), marks_ptr(e), e->ncells, lifetime, q, st));
-            else
-                HIPCHK(launch_grid_u32(e->d_hist32.as<uint32_t>(), marks_ptr(e),
-                                       e->d_out8.as<uint8_t>(), e->ncells, lifetime, q, st));
-        });
+    e->timed_on(GDF_KERNEL_GRID, st, [&] {
+        if (e->grid_mode == 0)
+            HIPCHK(launch_grid_u8(e->d_grid8.as<uint8_t>(), marks_ptr(e), e->ncells, lifetime, q, st));
+        else
+            HIPCHK(launch_grid_u32(e->d_hist32.as<uint32_t>(), marks_ptr(e),
+                                   e->d_out8.as<uint8_t>(), e->ncells, lifetime, q, st));
     });
     e->sl().marks_set = false;
     e->invoked_once = true;
@@ -2131,57 +2150,13 @@ int gdf_create(int device, gdf_engine** out) {
     if (!e) return GDF_ERR_NOMEM;
     e->device = device;
     int rc = guarded(e, [&] {
+        read_knobs(e);
         create_slot(e->slots[0]);
-        if (const char* v = std::getenv("GDF_SORT_PT")) e->sort_pt = std::atoi(v);  // tuning knob
-        // the engine's launch shapes (Tuning, gdf_device.hpp): a snapshot of the GDF_* variables
-        // at creation, read by this engine's launches only
-        auto knob = [](const char* name, uint32_t dflt, int lo = 0, int hi = INT32_MAX) {
-            const char* v = std::getenv(name);
-            return v ? (uint32_t)std::min(hi, std::max(lo, std::atoi(v))) : dflt;
-        };
-        const Tuning d;
-        Tuning& t = e->tune;
-        t.group_scan_tiles = knob("GDF_GROUP_SCAN_TILES", d.group_scan_tiles, 1);
-        t.run_stage = knob("GDF_RUN_STAGE", d.run_stage, 1);  // 512 or 2048
-        t.emit_px2 = knob("GDF_EMIT_PX2", d.emit_px2);
-        t.mask_occ8 = knob("GDF_MASK_OCC8", d.mask_occ8);
-        t.grid_wpt = knob("GDF_GRID_WPT", d.grid_wpt, 1, 8);
-        t.mask_px2 = knob("GDF_MASK_PX", d.mask_px2);  // pixels per k_mask thread
-        t.run_q16 = knob("GDF_RUN_Q16", d.run_q16);
-        t.group_first = knob("GDF_GROUP_FIRST", d.group_first);
-        t.run_wave_mode = knob("GDF_RUN_WAVE_MODE", d.run_wave_mode);
-        t.run_big_occ4 = knob("GDF_RUN_BIG_OCC4", d.run_big_occ4);
-        t.run_big_blocks = knob("GDF_RUN_BIG_BLOCKS", d.run_big_blocks, 1);
-        t.sort_blocks = knob("GDF_SORT_BLOCKS", d.sort_blocks, 1);
-        t.group_blocks = knob("GDF_GROUP_BLOCKS", d.group_blocks, 1);
-        t.run_inblock = knob("GDF_RUN_INBLOCK", d.run_inblock);
-        t.points_lane = knob("GDF_POINTS_LANE", d.points_lane);
-        t.run_wave = knob("GDF_RUN_WAVE", d.run_wave);
-        t.small_group = knob("GDF_SMALL_GROUP", d.small_group);
-        if (const char* v = std::getenv("GDF_SEG_ITEMS")) {  // tuning knob
-            const uint32_t si = (uint32_t)std::atoi(v);
-            if (si >= 64 && si <= kSegItems && si % 64 == 0) e->seg_items = si;
-        }
-        if (const char* v = std::getenv("GDF_SEL_SHAPE")) {  // tuning knob: "segs,threads"
-            unsigned sg = 0, th = 0;
-            if (std::sscanf(v, "%u,%u", &sg, &th) == 2 && (sg == 4 || sg == 8 || sg == 16) &&
-                th >= 128 && th <= 1024 && th % 64 == 0 && sg * (th / 64) <= 256) {
-                e->sel_segs = sg;
-                e->sel_threads = th;
-                e->sel_shape_set = true;
-            }
-        }
         ensure_misc(e);
         HIPCHK(hipStreamSynchronize(e->s()));
-        // every tuning variable this engine was created under (none changes a result; a stray
-        // one must not switch kernels silently): logged once, kept for gdf_get_tuning
-        for (const char* name : kTuningVars)
-            if (const char* v = std::getenv(name)) e->tuning_set += std::string(name) + "=" + v + " ";
-        if (!e->tuning_set.empty()) {
-            e->tuning_set.pop_back();
+        if (!e->tuning_set.empty())
             std::fprintf(stderr, "libgdf: engine on device %d created with tuning %s\n", device,
                          e->tuning_set.c_str());
-        }
     });
     if (rc != GDF_OK) {
         delete e;
@@ -2228,14 +2203,8 @@ int gdf_destroy(gdf_engine* e) {
         (void)hipEventDestroy(p.b);
     }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
-    if (e->grid_ev) (void)hipEventDestroy(e->grid_ev);
     for (Slot& sl : e->slots) {
         sl.graph.reset();
-        if (sl.dl_aux) {
-            (void)hipStreamSynchronize(sl.dl_aux);
-            (void)hipStreamDestroy(sl.dl_aux);
-        }
-        if (sl.dl_ev) (void)hipEventDestroy(sl.dl_ev);
         if (sl.h_misc) (void)hipHostFree(sl.h_misc);
         if (sl.h_stage) (void)hipHostFree(sl.h_stage);
         if (sl.h2d_done) (void)hipEventDestroy(sl.h2d_done);
@@ -2634,9 +2603,8 @@ int gdf_download_frame(gdf_engine* e, uint32_t what, gdf_host_frame* out) {
         if ((what & GDF_DL_GRID) && (!e->grid_set || !e->invoked_once))
             fail(GDF_ERR_STATE, "download_frame: no voxelOccupancyGrid has run");
         if (what & GDF_DL_GRID) sync_all(e);  // grid updates may still run on another slot's stream
-        if (q.pf_valid) {  // k_download wrote everything: the one wait (and the aux stream's)
+        if (q.pf_valid) {  // k_download wrote everything: the one wait
             e->sync();
-            if (q.dl_aux) HIPCHK(hipStreamSynchronize(q.dl_aux));
             q.pf_valid = false;
             Slot::Mirrors& M = q.mir[q.mir_pf];
             q.mir_out = q.mir_pf;  // (handed out: the next prefetch writes the other set)
@@ -3266,13 +3234,11 @@ int gdf_voxel_occupancy_grid_batch(gdf_engine* e, const uint32_t* bits, uint64_t
             for (uint32_t f0 = 0; f0 < nframes || f0 == 0; f0 += (uint32_t)kMaxCams) {
                 const uint32_t nf = std::min<uint32_t>(nframes - f0, (uint32_t)kMaxCams);
                 const GridSeq q = e->grid_seq(e->grid_ticket++);
-                e->grid_gated(e->s(), [&] {
-                    e->timed_on(GDF_KERNEL_GRID, e->s(), [&] {
-                        HIPCHK(launch_grid_u8_batch(e->d_grid8.as<uint8_t>(),
-                                                    bits ? bits + (uint64_t)f0 * frame_stride_words : bits,
-                                                    e->ncells, nranks, nf, frame_stride_words,
-                                                    rank_stride_words, lifetime, q, sn, e->s()));
-                    });
+                e->timed_on(GDF_KERNEL_GRID, e->s(), [&] {
+                    HIPCHK(launch_grid_u8_batch(e->d_grid8.as<uint8_t>(),
+                                                bits ? bits + (uint64_t)f0 * frame_stride_words : bits,
+                                                e->ncells, nranks, nf, frame_stride_words,
+                                                rank_stride_words, lifetime, q, sn, e->s()));
                 });
                 if (nframes == 0) break;
             }

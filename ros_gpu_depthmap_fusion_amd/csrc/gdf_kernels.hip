@@ -20,6 +20,7 @@
 #error "gdf_kernels.hip targets gfx950 (CDNA4) only: its coherence hand-offs use gfx950 cache bits"
 #endif
 #include "gdf_voxsum.hpp"  // the voxel sum (row_sum4): exact integer stretches
+#include "gdf_trace.hpp"   // GDF_TRACE(...): the diagnostic build's recorders, nothing in the product build
 
 #include <algorithm>
 
@@ -1294,25 +1295,10 @@ __device__ __forceinline__ unsigned long long part_lanes(unsigned long long m, b
 // rot45: 256 / PX threads per segment, the same band in LDS, the same outputs (validity word
 // w + j * waves from pixel j of wave w; counts, runs, run-key histogram).  No debug stage bits
 // (the engine launches k_mask for those).
-#ifdef GDF_TRACE_GROUPS
-// (diagnostic build, tools/mask_trace.py) per k_mask_px block: wall clock at entry and
-// exit, then wave 0's cycles in each phase - segment geometry and camera, band loads landed, LDS
-// stores + barrier, the filter, the ballots + publish barrier, the scan tail - each phase closed by
-// a wait for this wave's outstanding memory operations (which the product kernel does not do)
-constexpr uint32_t kMaskTraceSlots = 1u << 14;
-__device__ unsigned long long g_mtrace[kMaskTraceSlots][8];
-#define GDF_MSTAMP(i)               \
-    __builtin_amdgcn_s_waitcnt(0);  \
-    mt[i] = clock64()
-#endif
 
 template <int PX, int SEGW>
 __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
-#ifdef GDF_TRACE_GROUPS
-    const unsigned long long mw0 = wall_clock64();
-    unsigned long long mt[7] = {};
-    GDF_MSTAMP(0);
-#endif
+    GDF_TRACE(MaskTrace mt;)  // (entry stamp)
     constexpr int NT = SEGW / PX, NW = NT / 64;          // threads, waves
     constexpr int NWORDS = SEGW / 64;                    // validity words of a segment
     constexpr int NBR = 2 * 4 + 1;                       // band rows (h = 4)
@@ -1352,10 +1338,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
             const float *xn, *yn;
             uint32_t W, H;
         } c = {gcam[sg.k].depth, gcam[sg.k].xn, gcam[sg.k].yn, gcam[sg.k].W, gcam[sg.k].H};
-#ifdef GDF_TRACE_GROUPS
-        asm volatile("" ::"s"(c.depth), "s"(c.W));  // (the camera's fields before the stamp)
-        GDF_MSTAMP(1);
-#endif
+        GDF_TRACE(mt.stamp_after(1, c.depth, c.W);)
         const int h = 4;  // (F = 4: the launch checks it)
         const uint32_t ca = sg.x0 >= (uint32_t)h ? sg.x0 - h : 0u;
         const uint32_t cb = min(c.W, sg.x0 + sg.len + h);
@@ -1393,9 +1376,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
                 }
             }
         }
-#ifdef GDF_TRACE_GROUPS
-        GDF_MSTAMP(2);
-#endif
+        GDF_TRACE(mt.stamp(2);)
         const uint32_t tb = threadIdx.x;
         float xv[QX];
 #pragma unroll
@@ -1434,9 +1415,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
             if (ca + tb + (uint32_t)NT * q < cb) s_xn[tb + (uint32_t)NT * q] = xv[q];
         if (wrap && tb < (uint32_t)h) s_xn[-1 - (int)tb] = xwv;
         __syncthreads();
-#ifdef GDF_TRACE_GROUPS
-        GDF_MSTAMP(3);
-#endif
+        GDF_TRACE(mt.stamp(3);)
         const Band t{band, s_xn, s_rowoff, ca, h};
         const float* s_ynr = s_yn;
         if (64u * (uint32_t)wid < sg.len) {  // wave-uniform
@@ -1488,9 +1467,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
             }
         }
     }
-#ifdef GDF_TRACE_GROUPS
-    GDF_MSTAMP(4);
-#endif
+    GDF_TRACE(mt.stamp(4);)
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
         const uint32_t word = (uint32_t)wid + (uint32_t)NW * j;
@@ -1526,9 +1503,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
         }
     }
     __syncthreads();
-#ifdef GDF_TRACE_GROUPS
-    GDF_MSTAMP(5);
-#endif
+    GDF_TRACE(mt.stamp(5);)
     // (the first wave publishes the segment)
     if (wid == 0) {
         if (a.nparts) {  // counts [points of part 0..P-1 | runs of part 0..P-1][segment]
@@ -1558,15 +1533,7 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
     // reading the camera fields with scalar loads)
     if (a.grid_seq_out && blockIdx.x == 0 && threadIdx.x == 0) *a.grid_seq_out = a.grid_seq;
     group_scan_tail(a, s);
-#ifdef GDF_TRACE_GROUPS
-    GDF_MSTAMP(6);
-    if (threadIdx.x == 0 && blockIdx.x < kMaskTraceSlots) {
-        unsigned long long* g = g_mtrace[blockIdx.x];
-        g[0] = mw0;
-        g[1] = wall_clock64();
-        for (int k = 1; k < 7; ++k) g[k + 1] = mt[k] - mt[k - 1];
-    }
-#endif
+    GDF_TRACE(mt.store();)
 }
 
 template <int PX, int SEGW>
@@ -2209,13 +2176,6 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2_parts(FrameArgs a) {
 // voxel key) and run records straight to their place behind the depth compaction's - one pass
 // over the window, in selection order.  The last tile writes the frame's totals.  Stage bits go
 // to the debug buffer as before.
-#ifdef GDF_TRACE_GROUPS
-// (diagnostic build, tools/sel_trace.py) per k_sel tile: the wall clock (100 MHz) at block entry,
-// ticket, end of the counting pass (every wave past the barrier), end of the look-back, and block
-// end; the hardware id of wave 0
-constexpr uint32_t kSelTraceSlots = 1u << 16;
-__device__ unsigned long long g_strace[kSelTraceSlots][8];
-#endif
 template <uint32_t kSegs>
 __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
     constexpr uint32_t kSelSegs = kSegs;
@@ -2230,9 +2190,7 @@ __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
     const uint32_t B = blockDim.x, i = threadIdx.x;
     const bool stash = a.sel_key_lds != 0;  // (run mode, keys)
     const Tickets tk = tickets(a.sel_tiles, gridDim.x);  // (one tile per block: oneshot)
-#ifdef GDF_TRACE_GROUPS
-    const unsigned long long sw0 = wall_clock64();
-#endif
+    GDF_TRACE(SelTrace strace; strace.stamp(0);)
     // the depth compaction's totals (k_emit, earlier on the stream; the rollbuffer points and runs
     // go behind them): read now, in flight with the ticket, not after the look-back
     const uint32_t d = __builtin_amdgcn_readfirstlane(*G(a.out_count));
@@ -2245,9 +2203,7 @@ __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
     __syncthreads();
     const uint32_t tile = s_tile, epoch = s_epoch;
     if (a.grid_seq_out && tile == 0 && i == 0) *a.grid_seq_out = a.grid_seq;  // (as k_mask)
-#ifdef GDF_TRACE_GROUPS
-    const unsigned long long sw1 = wall_clock64();
-#endif
+    GDF_TRACE(strace.stamp(1);)
     const uint32_t si0 = tile * kSelSegs * B;
     float tc[12], tw[16];
     // the ring loads (their slots need no search; 32-bit slot arithmetic: ring_cap < 2^32),
@@ -2351,9 +2307,7 @@ __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
         }
     }
     __syncthreads();
-#ifdef GDF_TRACE_GROUPS
-    const unsigned long long sw2 = wall_clock64();
-#endif
+    GDF_TRACE(strace.stamp(2);)
     // exclusive scans of the (segment, wave) counts in item order: points by wave 0, runs by
     // wave 1 (<= 256 entries each)
     const uint32_t ne = kSelSegs * (uint32_t)nwaves;
@@ -2383,9 +2337,7 @@ __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
         }
     }
     __syncthreads();
-#ifdef GDF_TRACE_GROUPS
-    const unsigned long long sw3 = wall_clock64();
-#endif
+    GDF_TRACE(strace.stamp(3);)
     const uint32_t pbase = d + s_ex[0], rbase = rd + (a.run_mode ? s_ex[1] : 0u);
     if (tile == a.sel_tiles - 1u && i == 0) {  // the frame's totals
         *G(a.final_count) = pbase + s_tot[0];
@@ -2429,20 +2381,7 @@ __global__ __launch_bounds__(1024) void k_sel(FrameArgs a) {
         }
         if (a.do_voxel && a.marks) mark_and_count(a, a.marks, valid, key, key, nullptr, s_mark);
     }
-#ifdef GDF_TRACE_GROUPS
-    __syncthreads();
-    if (i == 0 && tile < kSelTraceSlots) {
-        unsigned long long* t = g_strace[tile];
-        t[0] = sw0;
-        t[1] = sw1;
-        t[2] = sw2;
-        t[3] = sw3;
-        t[4] = wall_clock64();
-        t[5] = ((unsigned)__builtin_amdgcn_s_getreg(4 | (15 << 11)) & 0xFFFFu) |  // HW_ID
-               (((unsigned long long)__builtin_amdgcn_s_getreg(20 | (15 << 11)) & 0xFu) << 16);  // XCC
-        t[6] = blockIdx.x;
-    }
-#endif
+    GDF_TRACE(strace.store(tile);)
 }
 
 struct HookScope {  // begin/end of one profiled launch
@@ -2471,6 +2410,99 @@ bool sel_key_lds_allowed(uint32_t bytes) {
     return ok && bytes <= 96u * 1024u;
 }
 
+// The compaction kernels (every kernel mask_kernel / emit_kernel can return): pointer, the name
+// gdf_get_frame_kernels reports, block threads (0: FrameArgs::seg_threads).  All take one FrameArgs.
+enum CompactionId {
+    kMaskPxO8_256, kMaskPx_256, kMaskPx_640, kMaskF4, kMaskRotF4, kMaskF0, kMaskRotF0,
+    kEmitParts_256, kEmitPx2_256, kEmitPx2_640, kEmitPlain, kCompactionKernels
+};
+struct CompactionKernel {
+    const void* k;
+    const char* name;
+    uint32_t threads;
+};
+static const CompactionKernel kCompaction[kCompactionKernels] = {
+    {reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>), "k_mask_px_o8<2,256>", 128},
+    {reinterpret_cast<const void*>(&k_mask_px<2, 256>), "k_mask_px<2,256>", 128},
+    {reinterpret_cast<const void*>(&k_mask_px<2, 640>), "k_mask_px<2,640>", 320},
+    {reinterpret_cast<const void*>(&k_mask<false, 4>), "k_mask<false,4>", 0},
+    {reinterpret_cast<const void*>(&k_mask<true, 4>), "k_mask<true,4>", 0},
+    {reinterpret_cast<const void*>(&k_mask<false, 0>), "k_mask<false,0>", 0},
+    {reinterpret_cast<const void*>(&k_mask<true, 0>), "k_mask<true,0>", 0},
+    {reinterpret_cast<const void*>(&k_emit_px2_parts<256>), "k_emit_px2_parts<256>", 128},
+    {reinterpret_cast<const void*>(&k_emit_px2<256>), "k_emit_px2<256>", 128},
+    {reinterpret_cast<const void*>(&k_emit_px2<640>), "k_emit_px2<640>", 320},
+    {reinterpret_cast<const void*>(&k_emit), "k_emit", 0},
+};
+
+// 640-pixel segments (single frames under 1 Mi pixels): two pixels per thread only from this many
+// segments (measured on MI355X, A/B on one box: 720p single frames, 1440 segments, 13.7 -> 14.4-14.9
+// Gpoints/s; VGA single frames, 480 segments = 2400 waves of 320 threads, 8.3 -> 7.6-8.1)
+constexpr uint32_t kPx640MinSegs = 1024;
+
+// k_mask for (rot45, F): F = 4 is the launch default, rings unrolled
+static CompactionId plain_mask(int rot45, uint32_t F) {
+    if (F == 4) return rot45 ? kMaskRotF4 : kMaskF4;
+    return rot45 ? kMaskRotF0 : kMaskF0;
+}
+
+// k_mask_px (2 pixels per thread) serves 256-pixel segments at F = 4 without rot45 (tuning knob
+// GDF_MASK_PX; 0 or 1: k_mask); k_mask everything else.  (The 4-pixel form is gone: slower, and its
+// compiler-made private copy of FrameArgs broke the G() camera-table reads, cam_table above.)  Measured on MI355X
+// (A/B on one box, dense frames, 2 pixels per thread vs k_mask): VGA 8-frame batches
+// 22.1 -> 23.7, 720p 4-frame batches 29.8 -> 32.6, 4K 30.9 -> 32.4 Gpoints/s
+static CompactionId mask_id(const FrameArgs& a) {
+    const Tuning& T = *a.tune;
+    if (T.mask_px2 >= 2 && a.do_flying && a.F == 4 && !a.rot45 && a.seg_threads == 256 && !a.dbg &&
+        a.band_rowb <= 64 * 16)
+        return T.mask_occ8 ? kMaskPxO8_256 : kMaskPx_256;
+    // (half 720p rows: single frames under 1 Mi pixels with enough segments to fill the chip)
+    if (T.mask_px2 >= 2 && a.do_flying && a.F == 4 && !a.rot45 && a.seg_threads == 640 && !a.dbg &&
+        a.band_rowb <= 2 * 64 * 16 && a.total_segs >= kPx640MinSegs)
+        return kMaskPx_640;
+    return plain_mask(a.rot45, a.do_flying ? a.F : 0u);
+}
+
+// k_emit_px2 (two pixels per thread) for 256-pixel segments unless Tuning::emit_px2 is cleared
+static CompactionId emit_id(const FrameArgs& a) {
+    if (a.nparts) return kEmitParts_256;
+    if (a.tune->emit_px2 && a.seg_threads == 256) return kEmitPx2_256;
+    if (a.tune->emit_px2 && a.seg_threads == 640 && a.total_segs >= kPx640MinSegs) return kEmitPx2_640;
+    return kEmitPlain;
+}
+
+const void* mask_kernel(const FrameArgs& a) { return kCompaction[mask_id(a)].k; }
+const void* emit_kernel(const FrameArgs& a) { return kCompaction[emit_id(a)].k; }
+
+// the compaction kernels that write the emit partition (FrameArgs::nparts)
+bool emit_partition_kernels(const FrameArgs& a) {
+    const CompactionId km = mask_id(a);
+    FrameArgs plain = a;
+    plain.nparts = 0;
+    return (km == kMaskPx_256 || km == kMaskPxO8_256) && emit_id(plain) == kEmitPx2_256;
+}
+
+const char* compaction_kernel_name(const void* k) {
+    for (const CompactionKernel& c : kCompaction)
+        if (c.k == k) return c.name;
+    return "?";
+}
+
+const void* frame_kernel(int which, int rot45, uint32_t F) {
+    if (which == 1) return kCompaction[kEmitPlain].k;
+    if (which == 2) return reinterpret_cast<const void*>(&k_sel<8>);
+    if (which == 4) return reinterpret_cast<const void*>(&k_sel<4>);
+    if (which == 5) return reinterpret_cast<const void*>(&k_sel<16>);
+    return kCompaction[plain_mask(rot45, F)].k;
+}
+
+static hipError_t launch_compaction(CompactionId id, const FrameArgs& a, size_t lds, hipStream_t s) {
+    const CompactionKernel& c = kCompaction[id];
+    void* args[] = {const_cast<FrameArgs*>(&a)};
+    return hipLaunchKernel(c.k, dim3(a.total_segs), dim3(c.threads ? c.threads : a.seg_threads), args,
+                           lds, s);
+}
+
 hipError_t launch_frame(const FrameArgs& a, hipStream_t s, LaunchHook* hook) {
     hipError_t e;
     if (a.total_segs == 0) {  // no depth survivors to count
@@ -2483,23 +2515,7 @@ hipError_t launch_frame(const FrameArgs& a, hipStream_t s, LaunchHook* hook) {
     } else {
         {
             HookScope hs(hook, GDF_KERNEL_MASK);
-            const size_t lds = (size_t)a.band_lds;
-            const void* km = mask_kernel(a);
-            if (km == reinterpret_cast<const void*>(&k_mask_px<2, 256>))
-                hipLaunchKernelGGL((k_mask_px<2, 256>), dim3(a.total_segs), dim3(128), lds, s, a);
-            else if (km == reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>))
-                hipLaunchKernelGGL((k_mask_px_o8<2, 256>), dim3(a.total_segs), dim3(128), lds, s, a);
-            else if (km == reinterpret_cast<const void*>(&k_mask_px<2, 640>))
-                hipLaunchKernelGGL((k_mask_px<2, 640>), dim3(a.total_segs), dim3(320), lds, s, a);
-            else if (km == reinterpret_cast<const void*>(&k_mask<true, 4>))
-                hipLaunchKernelGGL((k_mask<true, 4>), dim3(a.total_segs), dim3(a.seg_threads), lds, s, a);
-            else if (km == reinterpret_cast<const void*>(&k_mask<false, 4>))
-                hipLaunchKernelGGL((k_mask<false, 4>), dim3(a.total_segs), dim3(a.seg_threads), lds, s, a);
-            else if (a.rot45)
-                hipLaunchKernelGGL((k_mask<true, 0>), dim3(a.total_segs), dim3(a.seg_threads), lds, s, a);
-            else
-                hipLaunchKernelGGL((k_mask<false, 0>), dim3(a.total_segs), dim3(a.seg_threads), lds, s, a);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = launch_compaction(mask_id(a), a, (size_t)a.band_lds, s)) != hipSuccess) return e;
         }
         if (!a.fused_prefix && !a.grp_done) {  // (run mode: the point counts, then the run counts)
             HookScope hs(hook, GDF_KERNEL_SCAN);
@@ -2509,16 +2525,7 @@ hipError_t launch_frame(const FrameArgs& a, hipStream_t s, LaunchHook* hook) {
                 return e;
         }
         HookScope hs(hook, GDF_KERNEL_EMIT);
-        const void* ke = emit_kernel(a);
-        if (ke == reinterpret_cast<const void*>(&k_emit_px2_parts<256>))
-            hipLaunchKernelGGL(k_emit_px2_parts<256>, dim3(a.total_segs), dim3(128), 0, s, a);
-        else if (ke == reinterpret_cast<const void*>(&k_emit_px2<256>))
-            hipLaunchKernelGGL(k_emit_px2<256>, dim3(a.total_segs), dim3(128), 0, s, a);
-        else if (ke == reinterpret_cast<const void*>(&k_emit_px2<640>))
-            hipLaunchKernelGGL(k_emit_px2<640>, dim3(a.total_segs), dim3(320), 0, s, a);
-        else
-            hipLaunchKernelGGL(k_emit, dim3(a.total_segs), dim3(a.seg_threads), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_compaction(emit_id(a), a, 0, s)) != hipSuccess) return e;
     }
     if (a.sel_tiles) {  // rollbuffer points: one pass, behind the depth survivors
         HookScope hs(hook, GDF_KERNEL_SEL);
@@ -2532,85 +2539,6 @@ hipError_t launch_frame(const FrameArgs& a, hipStream_t s, LaunchHook* hook) {
             hipLaunchKernelGGL(k_sel<8>, dim3(a.sel_tiles), dim3(thr), lds, s, a);
     }
     return hipGetLastError();
-}
-
-// 640-pixel segments (single frames under 1 Mi pixels): two pixels per thread only from this many
-// segments (measured on MI355X, A/B on one box: 720p single frames, 1440 segments, 13.7 -> 14.4-14.9
-// Gpoints/s; VGA single frames, 480 segments = 2400 waves of 320 threads, 8.3 -> 7.6-8.1)
-constexpr uint32_t kPx640MinSegs = 1024;
-
-// k_mask_px (2 pixels per thread) serves 256-pixel segments at F = 4 without rot45 (tuning knob
-// GDF_MASK_PX; 0 or 1: k_mask); k_mask everything else.  (The 4-pixel form is gone: slower, and its
-// compiler-made private copy of FrameArgs broke the G() camera-table reads, cam_table above.)  Measured on MI355X
-// (A/B on one box, dense frames, 2 pixels per thread vs k_mask): VGA 8-frame batches
-// 22.1 -> 23.7, 720p 4-frame batches 29.8 -> 32.6, 4K 30.9 -> 32.4 Gpoints/s
-const void* mask_kernel(const FrameArgs& a) {
-    const Tuning& T = *a.tune;
-    if (T.mask_px2 >= 2 && a.do_flying && a.F == 4 && !a.rot45 && a.seg_threads == 256 && !a.dbg &&
-        a.band_rowb <= 64 * 16)
-        return T.mask_occ8 ? reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>)
-                           : reinterpret_cast<const void*>(&k_mask_px<2, 256>);
-    // (half 720p rows: single frames under 1 Mi pixels with enough segments to fill the chip)
-    if (T.mask_px2 >= 2 && a.do_flying && a.F == 4 && !a.rot45 && a.seg_threads == 640 && !a.dbg &&
-        a.band_rowb <= 2 * 64 * 16 && a.total_segs >= kPx640MinSegs)
-        return reinterpret_cast<const void*>(&k_mask_px<2, 640>);
-    return frame_kernel(0, a.rot45, a.do_flying ? a.F : 0u);
-}
-
-
-// k_emit_px2 (two pixels per thread) for 256-pixel segments unless Tuning::emit_px2 is cleared
-// the compaction kernels that write the emit partition (FrameArgs::nparts)
-bool emit_partition_kernels(const FrameArgs& a) {
-    const void* km = mask_kernel(a);
-    FrameArgs plain = a;
-    plain.nparts = 0;
-    return (km == reinterpret_cast<const void*>(&k_mask_px<2, 256>) ||
-            km == reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>)) &&
-           emit_kernel(plain) == reinterpret_cast<const void*>(&k_emit_px2<256>);
-}
-
-const void* emit_kernel(const FrameArgs& a) {
-    if (a.nparts) return reinterpret_cast<const void*>(&k_emit_px2_parts<256>);
-    if (a.tune->emit_px2 && a.seg_threads == 256) return reinterpret_cast<const void*>(&k_emit_px2<256>);
-    if (a.tune->emit_px2 && a.seg_threads == 640 && a.total_segs >= kPx640MinSegs)
-        return reinterpret_cast<const void*>(&k_emit_px2<640>);
-    return reinterpret_cast<const void*>(&k_emit);
-}
-
-// the names of every kernel mask_kernel / emit_kernel can return (gdf_get_frame_kernels): one
-// table, keyed on those pointers; a kernel missing from it is reported as "?"
-const char* compaction_kernel_name(const void* k) {
-    static const struct {
-        const void* k;
-        const char* name;
-    } names[] = {
-        {reinterpret_cast<const void*>(&k_mask_px_o8<2, 256>), "k_mask_px_o8<2,256>"},
-        {reinterpret_cast<const void*>(&k_mask_px<2, 256>), "k_mask_px<2,256>"},
-        {reinterpret_cast<const void*>(&k_mask_px<2, 640>), "k_mask_px<2,640>"},
-        {reinterpret_cast<const void*>(&k_mask<false, 4>), "k_mask<false,4>"},
-        {reinterpret_cast<const void*>(&k_mask<true, 4>), "k_mask<true,4>"},
-        {reinterpret_cast<const void*>(&k_mask<false, 0>), "k_mask<false,0>"},
-        {reinterpret_cast<const void*>(&k_mask<true, 0>), "k_mask<true,0>"},
-        {reinterpret_cast<const void*>(&k_emit_px2_parts<256>), "k_emit_px2_parts<256>"},
-        {reinterpret_cast<const void*>(&k_emit_px2<256>), "k_emit_px2<256>"},
-        {reinterpret_cast<const void*>(&k_emit_px2<640>), "k_emit_px2<640>"},
-        {reinterpret_cast<const void*>(&k_emit), "k_emit"},
-    };
-    for (const auto& n : names)
-        if (n.k == k) return n.name;
-    return "?";
-}
-
-const void* frame_kernel(int which, int rot45, uint32_t F) {
-    if (which == 1) return reinterpret_cast<const void*>(&k_emit);
-    if (which == 2) return reinterpret_cast<const void*>(&k_sel<8>);
-    if (which == 4) return reinterpret_cast<const void*>(&k_sel<4>);
-    if (which == 5) return reinterpret_cast<const void*>(&k_sel<16>);
-    if (F == 4)  // the launch default: rings unrolled
-        return rot45 ? reinterpret_cast<const void*>(&k_mask<true, 4>)
-                     : reinterpret_cast<const void*>(&k_mask<false, 4>);
-    return rot45 ? reinterpret_cast<const void*>(&k_mask<true, 0>)
-                 : reinterpret_cast<const void*>(&k_mask<false, 0>);
 }
 
 // per-camera ray factors (sh/convert_depthmap_to_points.glsl:68-69), one f32 division each
@@ -3458,8 +3386,8 @@ constexpr uint32_t kPersistBlocks = 2048;  // blocks of a persistent sort / grou
 // Staged groups of up to Tuning::small_group points are summed by their own thread
 // (thread_group_sum: the four component chains side by side, one group per lane, the groups of a
 // tile in parallel); longer ones by a wave (gdf_voxsum.hpp's stretch sums: a wave per group,
-// serial over a block's groups).  Tuning::points_lane: k_group's staged long groups by 4-lane
-// chains (measured slower on single VGA / 720p frames: 5.7 / 9.9 vs 6.1 / 11.6 Gpoints/s).
+// serial over a block's groups).  (k_group's staged long groups by 4-lane chains measured slower
+// on single VGA / 720p frames, 5.7 / 9.9 vs 6.1 / 11.6 Gpoints/s, and are gone.)
 
 // p[0] + ... + p[n-1] per component, in order, by one thread: blocks of 4 points alternate between
 // two register sets, the next block read while the current one is added (LDS latency off the
@@ -3658,8 +3586,7 @@ __global__ __launch_bounds__(kGroupThreads) __attribute__((amdgpu_waves_per_eu(7
     uint32_t* tile_ctr, uint32_t* epoch_word, uint32_t* err, uint32_t* hist, int average,
     VoxelParams vp, uint32_t* marks, const uint32_t* tile_base, uint4* __restrict__ bigq,
     uint32_t* __restrict__ bigcnt, uint32_t bigcap, uint32_t nframes, uint32_t fshift,
-    uint32_t* __restrict__ fvox, uint32_t small_max, uint32_t lane_chains,
-    const uint32_t* tile_gtot) {
+    uint32_t* __restrict__ fvox, uint32_t small_max, const uint32_t* tile_gtot) {
     __shared__ uint32_t s_wave[4];
     __shared__ uint32_t s_tile, s_epoch, s_excl, s_nbig, s_nq;
     __shared__ uint32_t s_start[kGroupThreads + 1];
@@ -3808,17 +3735,7 @@ __global__ __launch_bounds__(kGroupThreads) __attribute__((amdgpu_waves_per_eu(7
     }
     __syncthreads();
     const uint32_t nbig = s_nbig;
-    // staged long groups: 4 lanes each, one component chain per lane (16 groups per wave), or
-    // (lane_chains = 0) the 4 waves' stretch sums, wave = component
-    for (uint32_t b = ((uint32_t)lane >> 2) * 4u + (uint32_t)wid; lane_chains && b < nbig; b += 64u) {
-        const uint32_t li = s_big[b];
-        const uint32_t s = s_start[li], e = s_start[li + 1];
-        if (e - S0 > staged) continue;
-        const uint32_t c = (uint32_t)lane & 3u;
-        const float acc = lane_comp_chain(reinterpret_cast<const float*>(s_pts + (s - S0)) + c, e - s);
-        out[4 * (size_t)(s_excl + li) + c] = c < 3 ? acc / (float)(e - s) : acc;
-    }
-    for (uint32_t b = 0; !lane_chains && b < nbig; ++b) {  // staged: the 4 waves, wave = component
+    for (uint32_t b = 0; b < nbig; ++b) {  // staged long groups: the 4 waves' stretch sums, wave = component
         const uint32_t li = s_big[b];
         const uint32_t s = s_start[li], e = s_start[li + 1];
         if (e - S0 > staged) continue;  // (block-uniform)
@@ -4036,15 +3953,6 @@ __device__ __forceinline__ void fetch_rows4(const RunBatch& bt, uint32_t c, int*
     }
 }
 
-#ifdef GDF_TRACE_GROUPS
-// (diagnostic build, tools/group_trace.py) per queued group: wall clock start / end, points,
-// chunks, cycles in the sums / at the barriers / in the fetches, and the CU it ran on
-constexpr uint32_t kTraceSlots = 1u << 16;
-__device__ unsigned long long g_gtrace[kTraceSlots][8];
-#define GDF_TCLK(var) const unsigned long long var = clock64()
-#else
-#define GDF_TCLK(var)
-#endif
 
 // The sum of component wid of sorted runs [rs, re) (one 4-wave block); npts = the group's points.
 template <int Q>
@@ -4052,8 +3960,7 @@ __device__ __forceinline__ float block_stream_sum(const uint32_t* __restrict__ r
                                                   const uint32_t* __restrict__ rlen, uint32_t rs,
                                                   uint32_t re, const float4* __restrict__ pts,
                                                   int* s_mark, uint32_t* s_base,
-                                                  float (*s_soa)[kRowStride * Q], uint32_t& npts,
-                                                  unsigned long long* tr) {
+                                                  float (*s_soa)[kRowStride * Q], uint32_t& npts GDF_TRACE(, GroupTrace& tr)) {
     static_assert(Q % 4 == 0 && Q <= 16, "rows_chunk_sum takes up to 16 rows");
     constexpr uint32_t CH = 64u * Q, NB = 64u * kRunsPerLane;  // chunk points, batch runs
     const uint32_t wid = threadIdx.x >> 6;
@@ -4070,9 +3977,9 @@ __device__ __forceinline__ float block_stream_sum(const uint32_t* __restrict__ r
     uint32_t rb = rs, c = 0;
     while (true) {  // block-uniform: one chunk per iteration
         const uint32_t n = min(CH, cur.T - c);
-        GDF_TCLK(b0);
+        GDF_TRACE(tr.clk(0);)
         __syncthreads();  // every wave has summed the previous chunk
-        GDF_TCLK(b1);
+        GDF_TRACE(tr.clk(1);)
 #pragma unroll
         for (int i = 0; i < Q / 4; ++i) {
             const uint32_t k = kRowStride * (wid * (Q / 4) + i) + (threadIdx.x & 63);
@@ -4095,28 +4002,18 @@ __device__ __forceinline__ float block_stream_sum(const uint32_t* __restrict__ r
         } else if (!more) {
             fb.T = 0;
         }
-        GDF_TCLK(b2);
+        GDF_TRACE(tr.clk(2);)
         __syncthreads();  // the chunk is in LDS
-        GDF_TCLK(b3);
+        GDF_TRACE(tr.clk(3);)
         if (next_batch) {
             put_bases(fb, s_base);
             wave_sync();
         }
         if (more || next_batch) fetch_rows4<Q>(fb, cn, s_mark, s_base, pts, p);
-        GDF_TCLK(b4);
+        GDF_TRACE(tr.clk(4);)
         s = rows_chunk_sum(s_soa[wid], n, s, cm);
-        GDF_TCLK(b5);
-#ifdef GDF_TRACE_GROUPS
-        if (tr) {
-            tr[0] += (b1 - b0) + (b3 - b2);  // barriers
-            tr[1] += b2 - b1;                // LDS stores (waits for the loads)
-            tr[2] += b4 - b3;                // fetch issue
-            tr[3] += b5 - b4;                // sum
-            tr[4] += 1;
-        }
-#else
-        (void)tr;
-#endif
+        GDF_TRACE(tr.clk(5);)
+        GDF_TRACE(tr.chunk();)
         npts += n;
         if (more) {
             cur = fb;
@@ -4236,16 +4133,6 @@ __device__ __forceinline__ float wave_stream_sum(const uint32_t* __restrict__ rp
 // by a wave from LDS (wave_group_sum: per-wave transpose buffers, 59.4 instead of 37.6 KB of LDS -
 // 2 blocks per CU, not 4), 2 summed by 4 lanes each, one component chain per lane (16 groups per
 // wave, the tile's long groups dealt round-robin over the 4 waves).
-#ifdef GDF_TRACE_GROUPS
-// (diagnostic build, tools/gruns_trace.py) per k_group_runs tile: the wall clock (100 MHz) at block
-// entry, tile start, after the run records and block scans, after the tile's offset / last-group
-// end, after the staged sums, at the tile's end; the hardware id of wave 0, the block
-constexpr uint32_t kRunTraceSlots = 1u << 14;
-__device__ unsigned long long g_rtrace[kRunTraceSlots][8];
-#define GDF_RSTAMP(var) const unsigned long long var = wall_clock64()
-#else
-#define GDF_RSTAMP(var)
-#endif
 template <int kRunStage, int WAVE>
 __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ rvals,
@@ -4288,7 +4175,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
     if (!tile_base && blockIdx.x >= tk.nblk) return;
     if (!tile_base && threadIdx.x == 0) s_epoch = read_epoch(epoch_word);
     uint32_t walk = blockIdx.x;
-    GDF_RSTAMP(rw0);
+    GDF_TRACE(RunsTrace rt; rt.stamp(0);)
     for (bool first = true;; first = false) {  // persistent
         if (!first && !tile_base && tk.oneshot) return;
         // the tile's run records (key, predecessor's key, value), loaded unconditionally at clamped
@@ -4325,7 +4212,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
         __syncthreads();
         const uint32_t tile = s_tile, epoch = s_epoch;
         if (tile >= ntiles) return;  // block-uniform
-        GDF_RSTAMP(rw1);
+        GDF_TRACE(rt.stamp(1);)
         const uint32_t t0 = tile * kGroupThreads;
         const uint32_t i = t0 + threadIdx.x;
         const uint32_t tend = min(n, t0 + kGroupThreads);
@@ -4361,7 +4248,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
         s_off[threadIdx.x] = poff;
         if (threadIdx.x == 0) s_off[kGroupThreads] = ptotal;
         __syncthreads();
-        GDF_RSTAMP(rw2);
+        GDF_TRACE(rt.stamp(2);)
         if (wid == 0) {
             const uint32_t ex = tile_base ? s_excl
                                           : lookback2_wave(status, gstatus, tile, ntiles, total, epoch, err);
@@ -4433,7 +4320,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
         // of the run offsets), the other groups are queued
         const uint32_t W0 = total ? s_off[s_start[0] - t0] : 0u;
         __syncthreads();  // (the last group's end, s_start[total]; the extra runs)
-        GDF_RSTAMP(rw3);
+        GDF_TRACE(rt.stamp(3);)
         const uint32_t rend = tend + s_nx;  // runs with records here
         if constexpr (WAVE == 2) {
             // Windows of kRunStage staged positions, up to kRunPasses per tile: each window starts
@@ -4491,24 +4378,8 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
                 if (base == 0xFFFFFFFFu) break;  // block-uniform: nothing eligible left
             }
             __syncthreads();
-            GDF_RSTAMP(rw4);
-#ifdef GDF_TRACE_GROUPS
-            auto rtrace = [&]() {
-                if (threadIdx.x == 0 && tile < kRunTraceSlots) {
-                    unsigned long long* g = g_rtrace[tile];
-                    g[0] = rw0;
-                    g[1] = rw1;
-                    g[2] = rw2;
-                    g[3] = rw3;
-                    g[4] = rw4;
-                    g[5] = wall_clock64();
-                    g[6] = ((unsigned)__builtin_amdgcn_s_getreg(4 | (15 << 11)) & 0xFFFFu) |
-                           (((unsigned long long)__builtin_amdgcn_s_getreg(20 | (15 << 11)) & 0xFu) << 16);
-                    g[7] = blockIdx.x;
-                }
-            };
-            if (total == 0) rtrace();
-#endif
+            GDF_TRACE(rt.stamp(4);)
+            GDF_TRACE(if (total == 0) rt.store(tile);)
             if (total == 0) continue;  // block-uniform
             // queued groups: huge ones (>= kHugeGroup points) into the region at the top of the
             // queue that k_group_runs_big draws first (longest first bounds the tail: the C3
@@ -4557,9 +4428,7 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
                     else atomicOr(err, 8u);
                 }
             }
-#ifdef GDF_TRACE_GROUPS
-            rtrace();
-#endif
+            GDF_TRACE(rt.store(tile);)
         } else {
             bool inblock = false;
             if (threadIdx.x < total && average) {
@@ -4644,10 +4513,9 @@ __global__ __launch_bounds__(kGroupThreads) void k_group_runs(
 // draws further slots (qctr[1]) while any remain and streams the runs of each (records rps / rlen by sorted run, written by k_group_runs) from global memory
 // (block_stream_sum).  The queue was complete when this launch began; the first sort pass of the
 // next voxelize zeroes the counters.
-// OCC4: compiled for 4 waves per SIMD (128 VGPRs, ~40 of them spilled; tuning knob
-// GDF_RUN_BIG_OCC4), else 3 (167 VGPRs)
-template <int Q, bool OCC4 = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC4 ? 4 : 1, 8))) void k_group_runs_big(const uint32_t* __restrict__ rps,
+// 3 waves per SIMD (167 VGPRs; compiled for 4 - 128 VGPRs, ~40 of them spilled - it lost)
+template <int Q>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_group_runs_big(const uint32_t* __restrict__ rps,
                                                        const uint32_t* __restrict__ rlen,
                                                        const float4* __restrict__ pts,
                                                        float* __restrict__ out,
@@ -4669,14 +4537,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC4 ? 4 : 
     const uint32_t nh = __hip_atomic_load(qctr + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t nq = min(na + nh, bigq_cap);
     auto slot_of = [&](uint32_t j) { return j < nh ? bigq_cap - 1u - j : j - nh; };
-#ifdef GDF_TRACE_GROUPS
-    if (blockIdx.x == 0 && threadIdx.x == 0) {  // (the queue's two regions, in the last slot)
-        g_gtrace[kTraceSlots - 1][0] = 0;
-        g_gtrace[kTraceSlots - 1][1] = na;
-        g_gtrace[kTraceSlots - 1][2] = nh;
-        g_gtrace[kTraceSlots - 1][3] = bigq_cap;
-    }
-#endif
+    GDF_TRACE(GroupTrace tr; tr.queue(na, nh, bigq_cap);)
     // Every resident block / wave takes a first slot, further ones are drawn from the counter.
     // The grid is sized to the blocks the chip holds at once (launch_voxelize): a block that is
     // not resident yet must not hold a slot - with 1024 blocks, the C3 window's 100 K-point
@@ -4704,28 +4565,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC4 ? 4 : 
             if (wave_mode && t >= nh) break;  // (a normal slot: wave mode from here)
             const uint4 q = bigq[slot_of(t)];
             uint32_t np = 0;
-#ifdef GDF_TRACE_GROUPS
-            unsigned long long tr[5] = {0, 0, 0, 0, 0};
-            const unsigned long long w0 = wall_clock64(), c0 = clock64();
-            const float sum = block_stream_sum<Q>(rps, rlen, q.y, q.z, pts, s_mark, s_base[wid], s_soa, np, tr);
-            if (threadIdx.x == 128 && t < kTraceSlots) {  // (wave 2: z)
-                unsigned long long* g = g_gtrace[t];
-                g[0] = w0;
-                g[1] = wall_clock64();
-                g[2] = ((unsigned long long)np << 32) | (unsigned)tr[4];
-                g[3] = clock64() - c0;
-                g[4] = tr[0];
-                g[5] = tr[1];
-                g[6] = tr[2];
-                // HW_ID (hwreg 4: wave, simd, pipe, cu, sh, se) and XCC_ID (hwreg 20) bits 0..15
-                const unsigned long long hw = (unsigned)__builtin_amdgcn_s_getreg(4 | (15 << 11)) & 0xFFFFu;
-                const unsigned long long xcc = (unsigned)__builtin_amdgcn_s_getreg(20 | (15 << 11)) & 0xFu;
-                g[7] = tr[3] | (hw << 40) | (xcc << 56);
-            }
-#else
-            const float sum = block_stream_sum<Q>(rps, rlen, q.y, q.z, pts, s_mark, s_base[wid], s_soa, np,
-                                                       nullptr);
-#endif
+            GDF_TRACE(tr.begin();)
+            const float sum = block_stream_sum<Q>(rps, rlen, q.y, q.z, pts, s_mark, s_base[wid], s_soa,
+                                                  np GDF_TRACE(, tr));
+            GDF_TRACE(tr.store_block(t, np);)
             store_comp_mean(out + 4 * (size_t)q.x, wid, sum, np);
             if (threadIdx.x == 0) s_t = atomicAdd(qctr + 1, 1u);
             __syncthreads();
@@ -4752,59 +4595,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC4 ? 4 : 
         if (t >= nq) return;
         const uint4 q = bigq[slot_of(t)];
         uint32_t np = 0;
-#ifdef GDF_TRACE_GROUPS
-        const unsigned long long w0 = wall_clock64(), c0 = clock64();
-#endif
+        GDF_TRACE(tr.begin();)
         const float sum = wave_stream_sum(rps, rlen, q.y, q.z, pts, wmark, s_base[wid], wsoa, np);
         const uint32_t c = lane >> 4;
         if ((lane & 15u) == 0) out[4 * (size_t)q.x + c] = c < 3 ? sum / (float)np : sum;
-#ifdef GDF_TRACE_GROUPS
-        if (lane == 0 && t < kTraceSlots) {
-            unsigned long long* g = g_gtrace[t];
-            g[0] = w0;
-            g[1] = wall_clock64();
-            g[2] = ((unsigned long long)np << 32) | ((np + 255u) / 256u);
-            g[3] = clock64() - c0;
-            g[4] = g[5] = g[6] = 0;
-            const unsigned long long hw = (unsigned)__builtin_amdgcn_s_getreg(4 | (15 << 11)) & 0xFFFFu;
-            const unsigned long long xcc = (unsigned)__builtin_amdgcn_s_getreg(20 | (15 << 11)) & 0xFu;
-            g[7] = (hw << 40) | (xcc << 56);
-        }
-#endif
+        GDF_TRACE(tr.store_wave(t, np);)
         t = 0xFFFFFFFFu;
     }
 }
-
-#ifdef GDF_TRACE_GROUPS
-extern "C" int gdf_debug_group_trace(void* dst, size_t bytes) {  // (diagnostic build only)
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gtrace), std::min(bytes, sizeof(g_gtrace)), 0,
-                                    hipMemcpyDeviceToHost);
-}
-extern "C" int gdf_debug_group_trace_clear() {
-    static unsigned long long zero[kTraceSlots][8];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_gtrace), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-}
-extern "C" int gdf_debug_sel_trace(void* dst, size_t bytes) {  // (diagnostic build only)
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_strace), std::min(bytes, sizeof(g_strace)), 0,
-                                    hipMemcpyDeviceToHost);
-}
-extern "C" int gdf_debug_sel_trace_clear() {
-    static unsigned long long zero[kSelTraceSlots][8];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_strace), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-}
-extern "C" int gdf_debug_runs_trace(void* dst, size_t bytes) {  // (diagnostic build only)
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rtrace), std::min(bytes, sizeof(g_rtrace)), 0,
-                                    hipMemcpyDeviceToHost);
-}
-extern "C" int gdf_debug_runs_trace_clear() {
-    static unsigned long long zero[kRunTraceSlots][8];
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_rtrace), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
-}
-extern "C" int gdf_debug_mask_trace(void* dst, size_t bytes) {  // (diagnostic build only)
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_mtrace), std::min(bytes, sizeof(g_mtrace)), 0,
-                                    hipMemcpyDeviceToHost);
-}
-#endif
 
 uint32_t seg_sort_tiles(uint32_t nmax, uint32_t nframes) {
     return (nmax + kSortThreads * 8 - 1) / (kSortThreads * 8) + std::max<uint32_t>(nframes, 1u);
@@ -4843,21 +4641,19 @@ static void launch_sort_pass(uint32_t tiles, hipStream_t s, const uint32_t* kin,
 // Blocks of k_group_runs_big<8> / <16> the current device holds at once, cached per device (an
 // engine is bound to one device, but a process may drive several; the value is computed once per
 // device and kernel variant, races only recompute the same number)
-static uint32_t resident_big_blocks(bool q16, bool occ4) {
+static uint32_t resident_big_blocks(bool q16) {
     constexpr int kDev = 64;
-    static std::atomic<uint32_t> cache[kDev][4];
+    static std::atomic<uint32_t> cache[kDev][2];
     int dev = 0;
     (void)hipGetDevice(&dev);
-    std::atomic<uint32_t>* slot = dev >= 0 && dev < kDev ? &cache[dev][(q16 ? 1 : 0) + (occ4 ? 2 : 0)] : nullptr;
+    std::atomic<uint32_t>* slot = dev >= 0 && dev < kDev ? &cache[dev][q16 ? 1 : 0] : nullptr;
     uint32_t rb = slot ? slot->load(std::memory_order_relaxed) : 0u;
     if (rb) return rb;
     int per_cu = 0, cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, occ4 ? (q16 ? reinterpret_cast<const void*>(&k_group_runs_big<16, true>)
-                             : reinterpret_cast<const void*>(&k_group_runs_big<8, true>))
-                      : (q16 ? reinterpret_cast<const void*>(&k_group_runs_big<16>)
-                             : reinterpret_cast<const void*>(&k_group_runs_big<8>)), 256, 0);
+        &per_cu, q16 ? reinterpret_cast<const void*>(&k_group_runs_big<16>)
+                     : reinterpret_cast<const void*>(&k_group_runs_big<8>), 256, 0);
     // (the API can report one block per CU too many, MI355X_MICROARCH.md)
     rb = per_cu > 1 && cus > 0 ? (uint32_t)((per_cu - 1) * cus) : 256u;
     if (slot) slot->store(rb, std::memory_order_relaxed);
@@ -4896,9 +4692,6 @@ hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t s, LaunchHook* hoo
         // (a 9-bit last digit: radix_wide_last)
         const bool wide = p + 1 == npasses && remaining == 9;
         const uint32_t dbits = wide ? 9u : remaining >= 8 ? 8u : (remaining ? remaining : 1u);
-        const bool gate = p == 0 && a.grid8 != nullptr;
-        if (gate && a.grid_wait && (e = hipStreamWaitEvent(s, a.grid_wait, 0)) != hipSuccess) return e;
-        if (gate && a.grid_rec && a.grid_rec_early && (e = hipEventRecord(a.grid_rec, s)) != hipSuccess) return e;
         if (sort_tiles) {
             HookScope hs(hook, GDF_KERNEL_SORT);
             if (wide) {
@@ -4916,7 +4709,6 @@ hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t s, LaunchHook* hoo
                 launch_sort_pass<16, 256>(sort_tiles, s, kin, vin, kbuf[p & 1], vbuf[p & 1], a, p, dbits);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-        if (gate && a.grid_rec && !a.grid_rec_early && (e = hipEventRecord(a.grid_rec, s)) != hipSuccess) return e;
         kin = kbuf[p & 1];
         vin = vbuf[p & 1];
     }
@@ -4965,11 +4757,9 @@ hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t s, LaunchHook* hoo
         if (a.average) {
             if ((e = hipGetLastError()) != hipSuccess) return e;
             const bool q16 = T.run_q16 == 1 || (T.run_q16 == 2 && a.nframes <= 1);
-            const bool occ4 = T.run_big_occ4 != 0;
-            const uint32_t rb = resident_big_blocks(q16, occ4);
+            const uint32_t rb = resident_big_blocks(q16);
             const uint32_t big_blocks = std::min(std::min(T.run_big_blocks, rb), a.big_cap ? a.big_cap : rb);
-            auto kb = occ4 ? (q16 ? k_group_runs_big<16, true> : k_group_runs_big<8, true>)
-                           : (q16 ? k_group_runs_big<16, false> : k_group_runs_big<8, false>);
+            auto kb = q16 ? k_group_runs_big<16> : k_group_runs_big<8>;
             hipLaunchKernelGGL(kb, dim3(big_blocks), dim3(256), 0, s, kbuf[sorted_passes & 1],
                                vbuf[sorted_passes & 1], a.pts, reinterpret_cast<float*>(a.out), a.bigq,
                                a.bigq_cap, qctr, T.run_wave_mode);
@@ -4982,7 +4772,7 @@ hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t s, LaunchHook* hoo
                        reinterpret_cast<uint32_t*>(a.ctrs + kCtrEpoch), a.err, a.hist, a.average,
                        a.vp, a.group_marks, tile_base, tile_base ? a.bigq : nullptr,
                        a.bigcnt, bigcap, a.nframes, a.frame_shift, a.frame_vox_start,
-                       T.small_group, T.points_lane, tile_gtot);
+                       T.small_group, tile_gtot);
     if (tile_base && a.bigq && a.average) {
         if ((e = hipGetLastError()) != hipSuccess) return e;
         hipLaunchKernelGGL(k_group_big, dim3(2048), dim3(256), 0, s, vin, a.pts,

@@ -165,12 +165,6 @@ struct VoxelizeArgs {
     float4* out;
     uint32_t* out_count;
     const Tuning* tune;  // the engine's launch shapes (sort / group grids, group-phase forms)
-    // the stream gate of the grid update carried by the first radix pass (direct launches): wait
-    // for grid_wait before that pass, record grid_rec after it - or, grid_rec_early, right before
-    // it: the next update then waits until this one is next in its stream (dispatchable), not
-    // done (null: none, e.g. graph capture)
-    hipEvent_t grid_wait, grid_rec;
-    int grid_rec_early;
     // > 0: k_group_runs_big's grid capped at this many blocks (batches of small frames: their
     // queue is almost always empty, and the launch of a resident grid is chain time - C2 +1 %)
     uint32_t big_cap;

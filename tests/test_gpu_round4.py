@@ -258,3 +258,16 @@ def test_tuning_is_a_snapshot_per_engine(Engine):
     orc.processFrame(p)
     w = orc.downloadVoxelizedPoints()[:, :3]
     assert np.array_equal(vox_a[vs[7]:vs[8], :3].view(np.uint32), w.view(np.uint32))
+
+
+def test_tuning_reports_each_kind_of_knob(Engine):
+    """gdf_get_tuning names exactly the variable an engine was created under, whichever way the
+    engine reads it - a clamped integer, a presence flag, the two with parsers of their own - and
+    an engine created afterwards with all of them unset reports nothing.  (No frame is processed.)"""
+    knobs = {"GDF_GRID_WPT": "4", "GDF_NO_PACK_RUNS": "1", "GDF_SEL_SHAPE": "4,256",
+             "GDF_SEG_ITEMS": "128"}
+    unset = dict.fromkeys(knobs)
+    for name, value in knobs.items():
+        e = engine_with(Engine, **{**unset, name: value})
+        assert e.tuning() == f"{name}={value}", (name, e.tuning())
+    assert engine_with(Engine, **unset).tuning() == ""

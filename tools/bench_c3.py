@@ -136,7 +136,7 @@ def run_c3(width=1280, height=720, window=256, steps=20, ring=4, profile_steps=5
                          "GBps": round(model[name] / (tot / 1e3 / n) / 1e9, 1)}
     dom = max(per, key=lambda q: per[q]["avg_us"] * per[q]["launches_per_frame"]) if per else None
     achieved = per[dom]["GBps"] if per else 0.0
-    # PMC traffic per launch (profiles/pmc_traffic.json, tools/r5/pmc_secondary.sh) against the model
+    # PMC traffic per launch (profiles/pmc_traffic.json, tools/r5/pmc_secondary.sh in the git history) against the model
     pmc_key = "c3/%dx%d/w%d/%s" % (W, H, window, workload)
     try:
         rec = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(pmc_key, {})
