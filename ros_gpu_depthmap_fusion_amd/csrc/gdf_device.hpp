@@ -220,11 +220,11 @@ struct FrameArgs {
     uint32_t* run_count;        // runs of the frame (device)
     uint32_t* scan_total;       // scratch total of the segment-count scan
     uint32_t* run_total;        // runs of depth + rollbuffer points (k_sel's last tile)
-    // group scan (no scan launch, kFusedPrefixSegs < segments <= kScanGroup * kMaxScanGroups):
-    // the last k_mask block to finish in each group of kScanGroup segments scans the group's
-    // counts into group-local offsets (seg_offsets) and the group totals (grp_tot: point totals,
-    // then run totals); k_emit adds the totals of the groups before its own
-    uint32_t* grp_done;         // [groups] arrival counters (self-resetting)
+    // group totals (no scan launch, kFusedPrefixSegs < segments <= kScanGroup * kMaxScanGroups):
+    // each k_mask block adds its counts to the totals of its group of kScanGroup segments
+    // (grp_tot: point totals, then run totals); k_emit adds the totals of the groups before its
+    // own and the raw counts (seg_counts) before its own inside its group.  seg_offsets is not
+    // written.  Accumulators: zero when k_mask starts (VoxelizeArgs::zero, or the engine)
     uint32_t* grp_tot;          // [2 * groups]
     int32_t mask_packed;        // k_mask_px<2>: both pixels of a thread in packed f32 ops
     // emit partition (multi-GPU fused cloud, gdf_set_emit_partition): the compaction writes the

@@ -351,7 +351,12 @@ struct Slot {
     uint32_t snap_blocks = 0, snap_frames = 0;
     DevBuf d_pcnt, d_poff;          // multi-GPU key-range partition workspace
     DevBuf d_xcnt, d_xoff, d_xrk, d_xrs;  // runs of a received (point, key) list
-    DevBuf d_grpdone, d_grptot;     // in-kernel group scan of the segment counts
+    // group totals of the segment counts (FrameArgs::grp_tot): accumulators, zero when a
+    // compaction starts.  totals_dirty: a compaction added to them and no voxelize (whose first
+    // sort pass clears totals_words of them) has been launched since
+    DevBuf d_grptot;
+    bool totals_dirty = false;
+    uint32_t totals_words = 0;
     struct Pinned {                 // pinned host mirror (gdf_download_frame)
         void* p = nullptr;
         size_t bytes = 0;
@@ -387,7 +392,7 @@ struct Slot {
     DevBuf d_didx, d_ddata;         // the grid delta of this slot's single-frame update
     bool delta_valid = false;
     uint32_t delta_ticket = 0;      // ... and that update's sequence number
-    DevBuf d_ggdone, d_ggtot;       // ... and of the group phase's tile counts
+    DevBuf d_ggdone, d_ggtot;       // in-kernel group scan of the group phase's tile counts
     DevBuf d_wruns, d_runkeys, d_runstart;  // runs of equal keys
     bool runs_sel = false;          // ... counted in kRunTotal (frame with rollbuffer points)
     bool runs_valid = false;        // this frame's voxelize may sort runs
@@ -1567,14 +1572,16 @@ FrameArgs frame_args(gdf_engine* e, bool fused_voxel, bool compaction_marks = fa
     a.seg_offsets = e->sl().d_toffsets.as<uint32_t>();
     a.fused_prefix = a.total_segs <= kFusedPrefixSegs ? 1 : 0;
     a.mask_packed = e->mask_packed ? 1 : 0;
-    // above: the last k_mask block of each group of kScanGroup segments scans the group (no scan
-    // launches); k_emit sums the group totals before its own
+    // above: each k_mask block adds its counts to the totals of its group of kScanGroup segments
+    // (no scan launches); k_emit sums the group totals before its own and its group's counts
     const uint32_t ngroups = (a.total_segs + kScanGroup - 1) / kScanGroup;
     if (!a.fused_prefix && e->group_scan && ngroups <= kMaxScanGroups) {
         Slot& q = e->sl();
-        q.d_grpdone.ensure_zero((size_t)ngroups * 4, e->s());  // (self-resetting afterwards)
-        q.d_grptot.ensure((size_t)ngroups * 2 * 4);
-        a.grp_done = q.d_grpdone.as<uint32_t>();
+        // zero on entry: a new buffer here, else by the voxelize that followed the last
+        // compaction (voxelize_args) - or here, when none did (the stage-by-stage API)
+        if (!q.d_grptot.ensure_zero((size_t)ngroups * 2 * 4, e->s()) && q.totals_dirty)
+            HIPCHK(hipMemsetAsync(q.d_grptot.p, 0, (size_t)q.totals_words * 4, e->s()));
+        q.totals_dirty = false;
         a.grp_tot = q.d_grptot.as<uint32_t>();
     }
     // k_mask's LDS band: 2h+1 rows of 16-B chunks covering segw + 2h columns (+1 chunk of
@@ -1621,7 +1628,7 @@ FrameArgs frame_args(gdf_engine* e, bool fused_voxel, bool compaction_marks = fa
         t.run_mode = 1;
         t.key_hist = nullptr;
         t.fused_prefix = 0;
-        t.grp_done = t.grp_tot = nullptr;
+        t.grp_tot = nullptr;
         if (emit_partition_kernels(t)) {
             Slot& q = e->sl();
             const uint32_t segs = std::max<uint32_t>(a.total_segs, 1);
@@ -1647,6 +1654,10 @@ FrameArgs frame_args(gdf_engine* e, bool fused_voxel, bool compaction_marks = fa
     if (e->nframes > 1) {
         e->sl().d_fstart.ensure((size_t)(e->nframes + 1) * 4);
         a.frame_pt_start = e->sl().d_fstart.as<uint32_t>();
+    }
+    if (a.grp_tot) {  // (the launch follows)
+        e->sl().totals_dirty = true;
+        e->sl().totals_words = 2 * ngroups;
     }
     return a;
 }
@@ -1829,6 +1840,11 @@ VoxelizeArgs voxelize_args(gdf_engine* e, int average, int fused_grid_lifetime,
         delta_args(e, v.gseq, e->grid_ticket, e->nframes == 1);
         e->grid_ticket++;
         if (e->nframes > 1) v.snap = snap_args(e, fused_grid_blocks(e->ncells, e->tune.grid_wpt), e->nframes);
+    }
+    if (e->sl().totals_dirty) {  // the first sort pass clears the compaction's group totals
+        v.zero = e->sl().d_grptot.as<uint32_t>();
+        v.zero_words = e->sl().totals_words;
+        e->sl().totals_dirty = false;  // (the launch follows)
     }
     return v;
 }

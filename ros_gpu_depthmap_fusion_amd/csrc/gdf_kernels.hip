@@ -12,8 +12,8 @@
 #include <atomic>
 #include "gdf_kernels.hpp"
 
-// The fence-free hand-offs (publish_count / arrive_and_scan, grid_seq_enter / grid_seq_leave
-// <COHERENT>) rely on gfx950's cache policy bits: cpol sc1 = agent-coherent (write-through past the
+// The fence-free hand-offs (k_group_count's publish_count / arrive_and_scan, grid_seq_enter /
+// grid_seq_leave <COHERENT>) rely on gfx950's cache policy bits: cpol sc1 = agent-coherent (write-through past the
 // XCD's L2), with vmcnt(0) draining the stores.  The same bits mean something else on other
 // targets: device code is built for gfx950 only.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -745,13 +745,12 @@ __device__ __forceinline__ void load_cams(const FrameArgs& a, CamDesc* s_cams) {
     for (uint32_t w = threadIdx.x; w < words; w += blockDim.x) dst[w] = G(src)[w];
 }
 
-// In-kernel group scan of the segment counts (replaces k_scan_reduce + k_scan_counts above
-// kFusedPrefixSegs segments): after a block has written its counts, it counts itself in at its
-// group of kScanGroup consecutive segments; the group's last block (agent-scope release /
-// acquire: the blocks of a group may run on other XCDs) scans the group's point counts - and run
-// counts - into group-local exclusive offsets and writes the group totals, then re-arms the
-// counter for the next launch (graph replays included).  k_emit adds the totals of the groups
-// before its own (group_partials).
+// In-kernel group scan of k_group_count's tile counts: after a block has written a count, it
+// counts itself in at its group of kScanGroup consecutive tiles; the group's last block
+// (agent-scope release / acquire: the blocks of a group may run on other XCDs) scans the group's
+// counts into group-local exclusive offsets and writes the group total, then re-arms the counter
+// for the next launch (graph replays included).  k_group / k_group_runs add the totals of the
+// groups before their tile's (wave_group_prefix).
 // Generic form (counts stored by publish_count, from thread 0): entry `idx` of `nent` counts (cnt[q * stride + i] for series q < nser) was just
 // written by thread 0 of this block; the last arriver of idx's group scans the group.
 __device__ __forceinline__ void publish_count(uint32_t* p, uint32_t v) {
@@ -798,11 +797,25 @@ __device__ __forceinline__ void arrive_and_scan(uint32_t* done, const uint32_t* 
     if (lane == 0) __hip_atomic_store(done + g, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ void group_scan_tail(const FrameArgs& a, uint32_t s) {
-    __shared__ uint32_t s_last;
-    if (!a.grp_done) return;
-    arrive_and_scan(a.grp_done, a.seg_counts, a.seg_offsets, a.grp_tot, s, a.total_segs,
-                    a.run_mode ? 2 : 1, a.total_segs, &s_last);
+// Segment s's counts, from one thread of its k_mask block: plain stores - the only reader is
+// k_emit, behind the kernel boundary.  Above kFusedPrefixSegs segments (grp_tot) a segment that
+// kept anything also adds its counts to the totals of its group of kScanGroup consecutive segments
+// (point totals, then run totals), with adds whose result nobody reads: nothing waits for them,
+// and the block ends without a drain, an arrival or a barrier.  k_emit sums the totals of the
+// groups before its own and the counts before its own inside its group (group_partials): no scan
+// launch and no offsets in between.  The totals are accumulators, zero when k_mask starts: the
+// first sort pass of the frame's voxelize clears them for the next frame (k_sort_pass), the engine
+// where no voxelize came in between.
+__device__ __forceinline__ void store_seg_counts(const FrameArgs& a, uint32_t s, uint32_t t, uint32_t r) {
+    G(a.seg_counts)[s] = t;
+    if (a.run_mode) G(a.seg_counts)[a.total_segs + s] = r;  // run counts follow the point counts
+    if (a.grp_tot && t) {  // (a segment without points has no runs)
+        const uint32_t g = s / kScanGroup;
+        const uint32_t ng = (a.total_segs + kScanGroup - 1) / kScanGroup;
+        __hip_atomic_fetch_add(G(a.grp_tot) + g, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (a.run_mode)
+            __hip_atomic_fetch_add(G(a.grp_tot) + ng + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // the sum of the group totals gtot[0 .. idx / kScanGroup) by one wave (every lane gets it)
@@ -819,8 +832,9 @@ __device__ __forceinline__ uint32_t wave_group_prefix(const uint32_t* gtot, uint
     return sum;
 }
 
-// sum of the totals of the groups before segment s's group (group-scan form), into s_red per
-// wave (run mode: the run totals too, into s_red + 16)
+// sum of the totals of the groups before segment s's group, plus (wave 0) the counts of the
+// segments before s in its group - s's offset among the points - into s_red per wave (run mode:
+// the run totals and counts too, into s_red + 16)
 __device__ __forceinline__ void group_partials(const FrameArgs& a, uint32_t s, uint32_t* s_red) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint32_t g = s / kScanGroup;
@@ -843,6 +857,14 @@ __device__ __forceinline__ void group_partials(const FrameArgs& a, uint32_t s, u
             rsum += in ? w[q] : 0u;
         }
     }
+    if (wid == 0) {
+        const uint32_t n = s - g * kScanGroup;  // (< kScanGroup: one lane each, clamped index)
+        const uint32_t t = g * kScanGroup + min((uint32_t)lane, n ? n - 1u : 0u);
+        const uint32_t c = G(a.seg_counts)[t];
+        const uint32_t rc = a.run_mode ? G(a.seg_counts)[a.total_segs + t] : 0u;
+        sum += (uint32_t)lane < n ? c : 0u;
+        rsum += (uint32_t)lane < n ? rc : 0u;
+    }
     for (int o = 32; o > 0; o >>= 1) {
         sum += __shfl_xor(sum, o, 64);
         rsum += __shfl_xor(rsum, o, 64);
@@ -857,6 +879,7 @@ __device__ __forceinline__ void group_partials(const FrameArgs& a, uint32_t s, u
 // own geometry and depth loads, summed after them - one load round for both instead of two
 struct GroupPart {
     uint32_t v[4], w[4];
+    uint32_t c, rc;  // the count of the lane's segment of s's own group (wave 0 sums those before s)
 };
 __device__ __forceinline__ GroupPart group_partials_issue(const FrameArgs& a, uint32_t s) {
     GroupPart p;
@@ -869,6 +892,12 @@ __device__ __forceinline__ GroupPart group_partials_issue(const FrameArgs& a, ui
         p.v[q] = G(a.grp_tot)[t];
         p.w[q] = a.run_mode ? G(a.grp_tot)[ng + t] : 0u;
     }
+    // (every wave loads, at a clamped index: a branch on the wave would take the loads out of
+    // this round)
+    const uint32_t n = s - g * kScanGroup;
+    const uint32_t t = g * kScanGroup + min(threadIdx.x & 63u, n ? n - 1u : 0u);
+    p.c = G(a.seg_counts)[t];
+    p.rc = a.run_mode ? G(a.seg_counts)[a.total_segs + t] : 0u;
     return p;
 }
 __device__ __forceinline__ void group_partials_finish(const FrameArgs& a, uint32_t s,
@@ -883,6 +912,9 @@ __device__ __forceinline__ void group_partials_finish(const FrameArgs& a, uint32
         sum += in ? p.v[q] : 0u;
         rsum += in ? p.w[q] : 0u;
     }
+    const bool own = wid == 0 && (uint32_t)lane < s - g * kScanGroup;
+    sum += own ? p.c : 0u;
+    rsum += own ? p.rc : 0u;
     for (uint32_t t = threadIdx.x + 4u * blockDim.x; t < g; t += blockDim.x) {  // (rare: > 4 strides)
         sum += G(a.grp_tot)[t];
         if (a.run_mode) rsum += G(a.grp_tot)[ng + t];
@@ -1048,11 +1080,9 @@ __global__ __launch_bounds__(1024) void k_mask(FrameArgs a) {
     if (threadIdx.x == 0) {
         uint32_t t = 0, r = 0;
         for (int w = 0; w < nwaves; ++w) t += s_cnt[w];
-        publish_count(a.seg_counts + s, t);
-        if (a.run_mode) {
+        if (a.run_mode)
             for (int w = 0; w < nwaves; ++w) r += s_rcnt[w];
-            publish_count(a.seg_counts + a.total_segs + s, r);  // run counts follow the point counts
-        }
+        store_seg_counts(a, s, t, r);
     }
     if (a.run_mode && a.key_hist) {
         const gptr<uint32_t> rep = G(a.key_hist + (blockIdx.x % kHistReps) * 1024u);
@@ -1060,7 +1090,6 @@ __global__ __launch_bounds__(1024) void k_mask(FrameArgs a) {
             if (s_hist[j])
                 __hip_atomic_fetch_add(rep + j, s_hist[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    group_scan_tail(a, s);
 }
 
 // PX pixels per thread, ring by ring in lockstep (F = 4, no rot45): pixel j of thread i is
@@ -1516,11 +1545,9 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
         } else if (lane == 0) {
             uint32_t tt = 0, r = 0;
             for (int w = 0; w < NWORDS; ++w) tt += s_cnt[w];
-            publish_count(a.seg_counts + s, tt);
-            if (a.run_mode) {
+            if (a.run_mode)
                 for (int w = 0; w < NWORDS; ++w) r += s_rcnt[w];
-                publish_count(a.seg_counts + a.total_segs + s, r);
-            }
+            store_seg_counts(a, s, tt, r);
         }
     }
     if (a.run_mode && a.key_hist) {
@@ -1532,7 +1559,6 @@ __device__ __forceinline__ void mask_px_body(const FrameArgs& a) {
     // (stored after the descriptor reads: a global store before them keeps the compiler from
     // reading the camera fields with scalar loads)
     if (a.grid_seq_out && blockIdx.x == 0 && threadIdx.x == 0) *a.grid_seq_out = a.grid_seq;
-    group_scan_tail(a, s);
     GDF_TRACE(mt.store();)
 }
 
@@ -1793,13 +1819,12 @@ __global__ __launch_bounds__(1024) void k_emit(FrameArgs a) {
     const bool valid = i < len && ((m >> lane) & 1ull);
     uint32_t tot;
     const uint32_t wpre = wave_prefix(a, s, tot);
-    const uint32_t sbase = a.fused_prefix ? 0u : G(a.seg_offsets)[s];
+    const uint32_t sbase = a.fused_prefix || a.grp_tot ? 0u : G(a.seg_offsets)[s];
     // run mode: this segment's first run (the scan over points then runs: minus all points)
     uint32_t rbase = 0, rwpre = 0, rtot = 0;
     if (a.run_mode) {
-        if (!a.fused_prefix)  // (group scan: offsets local to the group's runs)
-            rbase = G(a.seg_offsets)[a.total_segs + s] -
-                    (a.grp_tot ? 0u : G(a.seg_offsets)[a.total_segs]);
+        if (!a.fused_prefix && !a.grp_tot)  // (one scan over points, then runs: minus all points)
+            rbase = G(a.seg_offsets)[a.total_segs + s] - G(a.seg_offsets)[a.total_segs];
         for (int w = 0; w < nwaves; ++w) {
             const uint32_t rc = G(a.wave_runs)[(size_t)s * 16 + w];
             rwpre += (w < wid) ? rc : 0u;
@@ -2070,12 +2095,11 @@ __global__ __launch_bounds__(SEGW / 2) void k_emit_px2(FrameArgs a) {
         pc[w] = (uint32_t)__popcll(vw[w]);
         rc[w] = 0u;
     }
-    const uint32_t sbase = a.fused_prefix ? 0u : G(a.seg_offsets)[s];
+    const uint32_t sbase = a.fused_prefix || a.grp_tot ? 0u : G(a.seg_offsets)[s];
     uint32_t rbase = 0;
     if (a.run_mode) {
-        if (!a.fused_prefix)  // (group scan: offsets local to the group's runs)
-            rbase = G(a.seg_offsets)[a.total_segs + s] -
-                    (a.grp_tot ? 0u : G(a.seg_offsets)[a.total_segs]);
+        if (!a.fused_prefix && !a.grp_tot)  // (one scan over points, then runs: minus all points)
+            rbase = G(a.seg_offsets)[a.total_segs + s] - G(a.seg_offsets)[a.total_segs];
 #pragma unroll
         for (int w = 0; w < NWORDS; ++w) rc[w] = G(a.wave_runs)[(size_t)s * 16 + w];
     }
@@ -2517,7 +2541,7 @@ hipError_t launch_frame(const FrameArgs& a, hipStream_t s, LaunchHook* hook) {
             HookScope hs(hook, GDF_KERNEL_MASK);
             if ((e = launch_compaction(mask_id(a), a, (size_t)a.band_lds, s)) != hipSuccess) return e;
         }
-        if (!a.fused_prefix && !a.grp_done) {  // (run mode: the point counts, then the run counts)
+        if (!a.fused_prefix && !a.grp_tot) {  // (run mode: the point counts, then the run counts)
             HookScope hs(hook, GDF_KERNEL_SCAN);
             const uint32_t m = a.nparts ? 2u * a.nparts * a.total_segs
                                         : a.run_mode ? 2u * a.total_segs : a.total_segs;
@@ -3230,8 +3254,13 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_pass(
     uint32_t* tile_ctr, uint32_t* epoch_word, uint32_t* err, uint32_t shift, uint32_t dbits,
     uint32_t grid_block0, uint4* grid, uint32_t* marks, uint64_t grid_nwords, uint32_t lifetime,
     GridSeq q, uint32_t nframes, uint32_t fshift, const uint32_t* __restrict__ fstart,
-    uint64_t mark_words, SnapArgs snap, uint32_t* qreset, const uint32_t* __restrict__ pack_rs) {
+    uint64_t mark_words, SnapArgs snap, uint32_t* qreset, const uint32_t* __restrict__ pack_rs,
+    uint32_t* __restrict__ zero, uint32_t zero_words) {
     constexpr int kTile = kSortThreads * PT;
+    // (first pass: the frame's k_emit has read the compaction's group totals - accumulators, zero
+    // again for the next frame's k_mask, store_seg_counts)
+    if (zero && blockIdx.x == 0)
+        for (uint32_t j = threadIdx.x; j < zero_words; j += kSortThreads) zero[j] = 0u;
     // (first pass: the run-group queue counters start from zero for this voxelize's k_group_runs)
     if (qreset && blockIdx.x == 0 && threadIdx.x == 0) {
         qreset[0] = 0u;
@@ -4635,7 +4664,8 @@ static void launch_sort_pass(uint32_t tiles, hipStream_t s, const uint32_t* kin,
                        a.nframes, a.frame_shift, a.frame_pt_start, a.mark_words,
                        a.snap,
                        p == 0 ? reinterpret_cast<uint32_t*>(a.ctrs + kCtrRunQueue) : nullptr,
-                       p == 0 && a.pack_runs ? a.run_start : nullptr);
+                       p == 0 && a.pack_runs ? a.run_start : nullptr,
+                       p == 0 ? a.zero : nullptr, a.zero_words);
 }
 
 // Blocks of k_group_runs_big<8> / <16> the current device holds at once, cached per device (an

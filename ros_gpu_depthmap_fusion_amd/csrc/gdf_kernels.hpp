@@ -168,6 +168,10 @@ struct VoxelizeArgs {
     // > 0: k_group_runs_big's grid capped at this many blocks (batches of small frames: their
     // queue is almost always empty, and the launch of a resident grid is chain time - C2 +1 %)
     uint32_t big_cap;
+    // optional: words block 0 of the first sort pass sets to zero - the group totals of the
+    // frame's compaction (FrameArgs::grp_tot), read by its k_emit, for the next frame's k_mask
+    uint32_t zero_words;
+    uint32_t* zero;
 };
 hipError_t launch_voxelize(const VoxelizeArgs& a, hipStream_t s, LaunchHook* hook = nullptr);
 size_t voxelize_status_words(uint32_t nmax, uint32_t key_bits);

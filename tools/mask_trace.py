@@ -5,7 +5,9 @@ libgdf_trace.so (`python tools/group_trace.py --build` builds it), on one isolat
 
 prints the launch's span, how the blocks' start times spread (the generations of resident blocks),
 and wave 0's cycles per phase - segment geometry and camera, band loads landed, LDS stores +
-barrier, the filter, ballots + publish barrier, the scan tail.  Each phase is closed by a wait for
+barrier, the filter, ballots + publish barrier, the tail behind it ("scan tail": once the
+arrive-and-scan of the group, now the count stores, the group-total adds and the histogram flush).
+Each phase is closed by a wait for
 the wave's outstanding memory operations, which the product kernel does not do: the phases are
 upper bounds of what each costs, and the span is longer than the product kernel's."""
 import ctypes as C
