@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gdf.h"
+#include "gdf_filter.h"
 #include "gdf_objects.hpp"
 #include "gdf_segment.h"
 
@@ -72,7 +73,10 @@ public:
     // are part of libgdf.so, so there is nothing to load.
     void init(const std::string& /*shaderPath*/) {}
 
-    void clear() { check(gdf_clear(h_)); }  // :725-732
+    void clear() {  // :725-732
+        check(gdf_clear(h_));
+        voxelized_ = false;
+    }
 
     // addDepthmap (:798-816); the depth image is borrowed until uploadDepthmaps, as in the
     // reference (the component keeps the cv_bridge image alive for the frame)
@@ -190,11 +194,43 @@ public:
     // voxelize (:1743-1756): on the GPU; m_points_voxelized is filled like the reference's
     void voxelize(bool average_voxels) {
         check(gdf_voxelize(h_, average_voxels ? 1 : 0));
+        voxelized_ = true;
         uint32_t n = count();
         m_points_voxelized.resize(n);
         check(gdf_download_voxelized_points(h_, reinterpret_cast<float*>(m_points_voxelized.data()),
                                             n, &n));
         m_points_voxelized.resize(n);
+    }
+    // radiusFilter / bypassRadiusFilter (component.cpp:414-421; the reference engine dropped their
+    // implementation, include/gdf_filter.h states the rule): the voxelized cloud if voxelize() ran
+    // since clear(), else the points, filtered on the GPU into m_points_filtered
+    template <class Vec3>
+    void radiusFilter(const Vec3& lower_bound, const Vec3& upper_bound, float radius,
+                      int min_neighbors) {
+        gdf_radius_filter_params p{};
+        for (int i = 0; i < 3; ++i) {  // (the component passes cv::Vec3f here: v[i]; glm: x/y/z)
+            p.lower[i] = axis(lower_bound, i, 0);
+            p.upper[i] = axis(upper_bound, i, 0);
+        }
+        p.radius = radius;
+        p.min_neighbors = min_neighbors < 0 ? 0u : (uint32_t)min_neighbors;
+        check(gdf_radius_filter(h_, voxelized_ ? GDF_RF_VOXELIZED : GDF_RF_POINTS, &p));
+        uint32_t n = 0;
+        check(gdf_get_filtered_count(h_, &n));
+        m_points_filtered.resize(n);
+        check(gdf_download_filtered_points(h_, reinterpret_cast<float*>(m_points_filtered.data()),
+                                           n, &n));
+        m_points_filtered.resize(n);
+    }
+    void bypassRadiusFilter() {
+        if (voxelized_) {
+            m_points_filtered = m_points_voxelized;
+            return;
+        }
+        uint32_t n = count();
+        m_points_filtered.resize(n);
+        check(gdf_download_points(h_, reinterpret_cast<float*>(m_points_filtered.data()), n, &n));
+        m_points_filtered.resize(n);
     }
     void voxelOccupancyGrid(uint32_t lifetime) { check(gdf_voxel_occupancy_grid(h_, lifetime)); }
     void downloadVoxelOccupancyGrid() {
@@ -394,6 +430,7 @@ public:
     std::vector<uint8_t> m_occupancyGrid;
     std::vector<vec4> m_points;
     std::vector<vec4> m_points_voxelized;
+    std::vector<vec4> m_points_filtered;  // (component.cpp:494)
     std::vector<uint32_t> m_voxelCoords;
     int m_numPoints = 0;
     MeasureTime m_measureTime;
@@ -486,6 +523,10 @@ private:
         m_rollBufferLastTimeSec = r.last_time_sec;
         m_rollBufferLastTimeNSec = r.last_time_nsec;
     }
+    template <class V>
+    static auto axis(const V& v, int i, int) -> decltype((float)v[0]) { return (float)v[i]; }
+    template <class V>
+    static float axis(const V& v, int i, long) { return i == 0 ? v.x : i == 1 ? v.y : v.z; }
     static void check(int rc) {
         if (rc != GDF_OK) throw std::runtime_error(std::string("gdf: ") + gdf_last_error());
     }
@@ -497,6 +538,7 @@ private:
     gdf_engine* h_ = nullptr;
     gdf_segmenter* seg_ = nullptr;
     int device_ = 0;
+    bool voxelized_ = false;  // voxelize() ran since clear()
     float lo_[3] = {0, 0, 0}, cs_[3] = {1, 1, 1};
     uint32_t gridSize_[3] = {0, 0, 0};
 };

@@ -11,9 +11,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB_PATH = os.path.join(PKG, "lib", "libgdf.so")
-SOURCES = ["gdf_kernels.hip", "gdf_segment.hip", "gdf_engine.cpp", "gdf_driver.cpp",
-           "gdf_fused.cpp"]
-HEADERS = ["gdf_device.hpp", "gdf_kernels.hpp", "gdf_voxsum.hpp", "gdf_trace.hpp"]
+SOURCES = ["gdf_kernels.hip", "gdf_segment.hip", "gdf_filter.hip", "gdf_engine.cpp",
+           "gdf_driver.cpp", "gdf_fused.cpp"]
+HEADERS = ["gdf_device.hpp", "gdf_kernels.hpp", "gdf_voxsum.hpp", "gdf_trace.hpp", "gdf_filter.hpp"]
 
 # Float contract of SURVEY.md Appendix A: no FMA contraction, correctly rounded / and sqrt.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -23,7 +23,8 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 def _deps():
     deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
-    deps += [os.path.join(ROOT, "include", h) for h in ("gdf.h", "gdf_driver.h", "gdf_segment.h", "gdf_fused.h")]
+    deps += [os.path.join(ROOT, "include", h) for h in ("gdf.h", "gdf_driver.h", "gdf_segment.h", "gdf_fused.h",
+                                                      "gdf_filter.h")]
     return deps
 
 

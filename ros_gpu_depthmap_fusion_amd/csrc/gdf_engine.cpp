@@ -28,6 +28,7 @@
 
 #include "gdf.h"
 #include "gdf_kernels.hpp"
+#include "gdf_filter.hpp"
 
 using namespace gdf;
 
@@ -398,6 +399,16 @@ struct Slot {
     bool runs_valid = false;        // this frame's voxelize may sort runs
     uint32_t nframes = 1;           // frames of the slot's last processed batch
     uint32_t n_total = 0;
+    // radius outlier filter (gdf_filter.h): this slot's workspace and filtered results
+    struct Filter {
+        DevBuf cell, rank, cnt, start, cell_sums, sorted, scell, keep, tile_cnt, tile_off, tile_sums;
+        DevBuf out, count;
+        bool cnt_dirty = false;     // a failed call may have left cell counters set: cleared first
+        bool valid = false;         // a filter ran on this slot's frame (until its next gdf_clear)
+        uint32_t cap = 0;           // points the results can hold (the source's capacity)
+    } rf;
+    bool frame_pts = false, frame_vox = false;  // compaction / voxelize launched since gdf_clear
+    bool frame_parts = false;       // ... for a frame armed with the emit partition
     // steady-state frames as HIP graphs (the fused frame + voxelize launches of this slot): one
     // graph launch and two kernel-node argument updates (depth pointers, grid ticket) per frame
     // instead of six direct launches.  A graph is replayed while the frame's launch arguments -
@@ -551,6 +562,9 @@ struct gdf_engine {
         uint32_t *run_keys = nullptr, *run_starts = nullptr, *counts = nullptr;
         uint32_t nseg = 1;  // gdf_set_partition_segments: [depth | rollbuffer pieces] buckets
     } epart;
+    // gdf_set_radius_filter: single frames of gdf_process_frame end with the filter (sticky)
+    bool rf_armed = false;
+    gdf_radius_filter_params rf_params{};
     bool emit_part = true;  // GDF_NO_EMIT_PART (else: compaction, then the partition pass)
     // a frame armed with gdf_set_emit_partition sets its occupancy marks (gdf_set_partition_marks:
     // off when the caller builds the union from the key-range voxelize, gdf_voxelize_runs_marked)
@@ -811,6 +825,8 @@ void next_slot(gdf_engine* e) {
 void engine_clear(gdf_engine* e) {  // fusion.cpp:725-732
     next_slot(e);
     e->sl().pf_valid = false;
+    e->sl().rf.valid = false;
+    e->sl().frame_pts = e->sl().frame_vox = e->sl().frame_parts = false;
     e->nframes = 1;
     e->rb.selection_point_count = 0;
     e->rb.selection_sequence_count = 0;
@@ -1669,6 +1685,9 @@ void frame_launched(gdf_engine* e, bool fused_voxel, bool key_hist, bool runs = 
     e->sl().coords_valid = fused_voxel;
     e->sl().marks_set = fused_voxel;
     e->sl().vox_valid = false;
+    e->sl().frame_pts = true;
+    e->sl().frame_vox = false;
+    e->sl().frame_parts = false;
 }
 
 // the kernels launch_frame resolves for these arguments, direct or captured (a graph replay runs
@@ -1690,6 +1709,7 @@ void run_frame(gdf_engine* e, bool fused_voxel, bool compaction_marks = false) {
     if (a.nparts) {  // (the points went to the send lists only: no compaction-order outputs)
         e->sl().coords_valid = false;
         e->sl().runs_valid = false;
+        e->sl().frame_parts = true;
     }
 }
 
@@ -1858,6 +1878,7 @@ void voxelize_launched(gdf_engine* e, int fused_grid_lifetime) {
     }
     e->sl().khist_pending = false;
     e->sl().vox_valid = true;
+    e->sl().frame_vox = true;
 }
 
 void voxelize(gdf_engine* e, int average, int fused_grid_lifetime = -1) {
@@ -2122,6 +2143,103 @@ void partition_runs(gdf_engine* e, uint32_t nparts, float* send_pts, uint32_t* s
                                 q.nframes > 1 ? e->key_bits : 0u, send_run_keys, send_run_starts,
                                 split, nseg - 1, q.sel_frame ? 1u : 0u));
     }
+}
+
+// ---- radius outlier filter (include/gdf_filter.h, gdf_filter.hip) -------------------------------
+// n = n_dev ? min(*n_dev, n_cap) : n_cap points of `in`; keep == nullptr: the slot's own flags
+void radius_filter_run(gdf_engine* e, const float4* in, const uint32_t* n_dev, uint32_t n_cap,
+                       const gdf_radius_filter_params* p, float4* out, uint32_t* out_count,
+                       uint8_t* keep) {
+    RadiusPlan pl;
+    if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    if (n_cap > (1u << 31)) fail(GDF_ERR_ARG, "radius filter: more than 2^31 points");
+    Slot::Filter& w = e->sl().rf;
+    hipStream_t st = e->s();
+    const size_t nb = std::max<uint32_t>(n_cap, 1u);
+    const uint32_t nt = std::max<uint32_t>(rf_tiles(n_cap), 1u);
+    w.cell.ensure(nb * 4);
+    w.rank.ensure(nb * 4);
+    w.sorted.ensure(nb * 16);
+    w.scell.ensure(nb * 4);
+    if (!keep) w.keep.ensure(nb);
+    w.start.ensure(((size_t)pl.ncells + 1) * 4);
+    w.cell_sums.ensure(rf_scan_words(pl.ncells) * 4);
+    w.tile_cnt.ensure(((size_t)nt + 1) * 4);
+    w.tile_off.ensure(((size_t)nt + 1) * 4);
+    w.tile_sums.ensure(rf_scan_words(nt) * 4);
+    // the cell counters are zero between calls (the scan that reads them last clears them); a
+    // grown buffer, or one a failed call may have left set, is cleared whole
+    if (!w.cnt.ensure_zero(((size_t)pl.ncells + 1) * 4, st) && w.cnt_dirty)
+        HIPCHK(hipMemsetAsync(w.cnt.p, 0, w.cnt.bytes, st));
+    RadiusArgs a{};
+    a.in = in;
+    a.n_dev = n_dev;
+    a.n_cap = n_cap;
+    for (int k = 0; k < 3; ++k) {
+        a.lo[k] = p->lower[k];
+        a.hi[k] = p->upper[k];
+        a.inv[k] = pl.inv[k];
+        a.cells[k] = pl.cells[k];
+    }
+    a.ncells = pl.ncells;
+    a.r2 = pl.r2;
+    a.min_neighbors = p->min_neighbors;
+    a.cell = w.cell.as<uint32_t>();
+    a.rank = w.rank.as<uint32_t>();
+    a.cnt = w.cnt.as<uint32_t>();
+    a.start = w.start.as<uint32_t>();
+    a.cell_sums = w.cell_sums.as<uint32_t>();
+    a.sorted = w.sorted.as<float4>();
+    a.scell = w.scell.as<uint32_t>();
+    a.keep = keep ? keep : w.keep.as<uint8_t>();
+    a.tile_cnt = w.tile_cnt.as<uint32_t>();
+    a.tile_off = w.tile_off.as<uint32_t>();
+    a.tile_sums = w.tile_sums.as<uint32_t>();
+    a.out = out;
+    a.out_count = out_count;
+    w.cnt_dirty = true;
+    HIPCHK(launch_radius_filter(a, st));
+    w.cnt_dirty = false;
+}
+
+// the stage call: the addressed slot's points or voxelized points, count on the device
+void radius_filter_stage(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
+    Slot& q = e->sl();
+    if (source != GDF_RF_POINTS && source != GDF_RF_VOXELIZED) fail(GDF_ERR_ARG, "radius filter: bad source");
+    if (q.nframes > 1 && q.frame_pts) fail(GDF_ERR_STATE, "radius filter: not for a multi-frame batch");
+    if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "radius filter before the frame's compaction");
+    if (q.frame_parts)
+        fail(GDF_ERR_STATE, "radius filter: not for a frame armed with the emit partition");
+    const float4* in;
+    const uint32_t* n_dev;
+    uint32_t cap;
+    if (source == GDF_RF_VOXELIZED) {
+        if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "radius filter before the frame's voxelize");
+        in = q.d_vox.as<float4>();
+        n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
+        cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, 1u << 31);
+    } else {
+        in = q.d_pts.as<float4>();
+        n_dev = q.d_misc.as<uint32_t>() + kCount;
+        cap = q.n_total;
+    }
+    RadiusPlan pl;
+    if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    q.rf.valid = false;
+    q.rf.out.ensure((size_t)std::max<uint32_t>(cap, 1u) * 16);
+    q.rf.count.ensure(256);
+    q.rf.cap = cap;
+    radius_filter_run(e, in, n_dev, cap, p, q.rf.out.as<float4>(), q.rf.count.as<uint32_t>(), nullptr);
+    q.rf.valid = true;
+}
+
+uint32_t filtered_count(gdf_engine* e) {
+    Slot& q = e->sl();
+    if (!q.rf.valid) fail(GDF_ERR_STATE, "no radius filter ran on this frame");
+    uint32_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, q.rf.count.p, 4, hipMemcpyDeviceToHost, e->s()));
+    e->sync();
+    return std::min(n, q.rf.cap);
 }
 
 }  // namespace
@@ -2796,6 +2914,11 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
                                     "(gdf_take_occupancy_marks + gdf_voxel_occupancy_grid_batch)");
             if (e->nframes > kMaxCams) fail(GDF_ERR_ARG, "at most 16 frames per batch");
         }
+        if (e->rf_armed) {  // (before anything is launched)
+            if (e->nframes > 1) fail(GDF_ERR_STATE, "radius filter armed: not for a multi-frame batch");
+            if (p->enable_voxel_filter && p->defer_voxelize)
+                fail(GDF_ERR_STATE, "radius filter armed: not for a deferred-voxelize frame");
+        }
         res.processed = 1;
         upload_point_sequences(e);
         e->ps_filter_set = true;
@@ -2838,6 +2961,7 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
                     fail(GDF_ERR_CAPACITY, "emit partition: send lists smaller than the frame");
                 run_frame(e, true, true);
                 e->epart = gdf_engine::EmitPart{};  // (one frame)
+                if (ep.nparts) e->sl().frame_parts = true;  // (whichever way the lists were written)
                 if (ep.nparts && !e->sl().part_emitted)  // the compaction could not: a pass
                     partition_runs(e, ep.nparts, ep.pts, ep.run_keys, ep.run_starts, ep.cap, ep.counts,
                                    ep.nseg);
@@ -2852,6 +2976,9 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
         } else {
             run_frame(e, false);
         }
+        if (e->rf_armed)  // after the frame's chain, outside its captured graph
+            radius_filter_stage(e, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
+                                &e->rf_params);
         res.num_depth_points = e->depth_total;
         res.num_points_total = e->sl().n_total;
         if (p->synchronous) {
@@ -2893,6 +3020,65 @@ int gdf_transform_points(gdf_engine* e, const float* in, const uint32_t* mask, f
         if (!T || (n && (!in || !mask || !out))) fail(GDF_ERR_ARG, "transform_points: null argument");
         HIPCHK(launch_transform_points(reinterpret_cast<const float4*>(in), mask,
                                        reinterpret_cast<float4*>(out), n, T, e->s()));
+    });
+}
+
+int gdf_radius_filter_points(gdf_engine* e, const float* in, uint32_t n,
+                             const gdf_radius_filter_params* p, float* out, uint32_t* out_count,
+                             uint8_t* keep) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (!p || !out_count || (n && (!in || !out))) fail(GDF_ERR_ARG, "radius filter: null argument");
+        if (n && in == out) fail(GDF_ERR_ARG, "radius filter: in-place is not supported");
+        radius_filter_run(e, reinterpret_cast<const float4*>(in), nullptr, n, p,
+                          reinterpret_cast<float4*>(out), out_count, keep);
+    });
+}
+
+int gdf_radius_filter(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (!p) fail(GDF_ERR_ARG, "radius filter: null parameters");
+        radius_filter_stage(e, source, p);
+    });
+}
+
+int gdf_set_radius_filter(gdf_engine* e, int enable, const gdf_radius_filter_params* p) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (enable) {
+            RadiusPlan pl;
+            if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+            e->rf_params = *p;
+        }
+        e->rf_armed = enable != 0;
+    });
+}
+
+int gdf_get_filtered_count(gdf_engine* e, uint32_t* out) {
+    ENGINE_OR_FAIL(e);
+    if (!out) return GDF_ERR_ARG;
+    return guarded(e, [&] { *out = filtered_count(e); });
+}
+
+int gdf_download_filtered_points(gdf_engine* e, float* out, uint32_t cap, uint32_t* out_count) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        const uint32_t n = filtered_count(e);
+        if (out_count) *out_count = n;
+        if (out) {
+            if (cap < n) fail(GDF_ERR_CAPACITY, "filtered points: buffer too small");
+            if (n) HIPCHK(hipMemcpy(out, e->sl().rf.out.p, (size_t)n * 16, hipMemcpyDeviceToHost));
+        }
+    });
+}
+
+int gdf_get_device_filtered(gdf_engine* e, const float** pts, const uint32_t** count) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (!e->sl().rf.valid) fail(GDF_ERR_STATE, "no radius filter ran on this frame");
+        if (pts) *pts = e->sl().rf.out.as<const float>();
+        if (count) *count = e->sl().rf.count.as<const uint32_t>();
     });
 }
 
@@ -3035,6 +3221,7 @@ void voxelize_runs(gdf_engine* e, const float* pts, const uint32_t* run_keys, ui
     }
     e->timed(GDF_KERNEL_VOXELIZE, [&] { HIPCHK(launch_voxelize(v, e->s(), e->hook_ptr())); });
     e->sl().vox_valid = true;
+    e->sl().frame_vox = true;
 }
 }  // namespace
 
@@ -3095,6 +3282,7 @@ int gdf_voxelize_points(gdf_engine* e, const float* pts, const uint32_t* keys, u
         e->timed(GDF_KERNEL_VOXELIZE, [&] { HIPCHK(launch_voxelize(v, e->s(), e->hook_ptr())); });
         e->sl().khist_pending = false;
         e->sl().vox_valid = true;
+        e->sl().frame_vox = true;
     });
 }
 

@@ -115,6 +115,15 @@ class LocalOp(C.Structure):
                 ("bytes", C.c_uint64), ("peer", C.c_int)]
 
 
+class RadiusFilterParams(C.Structure):
+    """gdf_radius_filter_params (include/gdf_filter.h)."""
+    _fields_ = [("lower", _f3), ("upper", _f3), ("radius", C.c_float),
+                ("min_neighbors", C.c_uint32)]
+
+
+RF_POINTS, RF_VOXELIZED = 0, 1
+
+
 class GDFError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"{STATUS_NAMES.get(status, status)}: {msg}")
@@ -162,6 +171,10 @@ EXPORTED = [
     "gdf_seg_download_num_labels", "gdf_seg_download_stats", "gdf_seg_download_connections",
     "gdf_seg_download_contours", "gdf_seg_merge_labels", "gdf_seg_get_device_results",
     "gdf_seg_create_objects",
+    # include/gdf_filter.h: the radius outlier filter
+    "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
+    "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
+    "gdf_get_device_filtered",
 ]
 
 
@@ -293,6 +306,13 @@ def load_library(path: str = LIB_PATH):
         "gdf_seg_merge_labels": (i32, [vp, vp, u32, P(u32)]),
         "gdf_seg_get_device_results": (i32, [vp, P(vp), P(vp), P(vp), P(vp)]),
         "gdf_seg_create_objects": (i32, [vp, vp, vp, vp, u32, vp, u32, P(u32)]),
+        "gdf_radius_filter_plan": (i32, [P(RadiusFilterParams), vp, vp]),
+        "gdf_radius_filter_points": (i32, [vp, vp, u32, P(RadiusFilterParams), vp, vp, vp]),
+        "gdf_radius_filter": (i32, [vp, i32, P(RadiusFilterParams)]),
+        "gdf_set_radius_filter": (i32, [vp, i32, P(RadiusFilterParams)]),
+        "gdf_get_filtered_count": (i32, [vp, P(u32)]),
+        "gdf_download_filtered_points": (i32, [vp, vp, u32, P(u32)]),
+        "gdf_get_device_filtered": (i32, [vp, P(vp), P(vp)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -323,6 +343,30 @@ def build_info(lib=None) -> dict:
             k, v = kv.split("=", 1)
             out[k] = v
     return out
+
+
+def radius_filter_params(lower, upper, radius, min_neighbors) -> RadiusFilterParams:
+    """gdf_radius_filter_params from Python values (radius rounded to float32)."""
+    p = RadiusFilterParams()
+    p.lower = _f3(*[float(x) for x in lower])
+    p.upper = _f3(*[float(x) for x in upper])
+    p.radius = float(radius)
+    p.min_neighbors = int(min_neighbors)
+    return p
+
+
+def radius_filter_plan(lower, upper, radius, min_neighbors=0):
+    """The radius filter's cell plan (gdf_radius_filter_plan; no engine, no GPU):
+    ((cells_x, cells_y, cells_z), float32 edge[3]).  Raises GDFError(GDF_ERR_ARG) for parameters
+    the filter refuses."""
+    lib = load_library()
+    p = radius_filter_params(lower, upper, radius, min_neighbors)
+    cells = np.zeros(3, np.uint32)
+    edge = np.zeros(3, np.float32)
+    rc = lib.gdf_radius_filter_plan(C.byref(p), _ptr(cells), _ptr(edge))
+    if rc != GDF_OK:
+        raise GDFError(rc, lib.gdf_last_error().decode())
+    return tuple(int(c) for c in cells), edge
 
 
 def _ptr(a: Optional[np.ndarray]):
@@ -867,6 +911,48 @@ class GPUDepthmapFusion:
         self._check(self._lib.gdf_transform_points(self._h, C.c_void_p(in_ptr),
                                                    C.c_void_p(mask_ptr), C.c_void_p(out_ptr),
                                                    num_items, _ptr(t)))
+
+    # ---- radius outlier filter (include/gdf_filter.h) ----
+    def radiusFilterPoints(self, in_ptr: int, n: int, params: RadiusFilterParams, out_ptr: int,
+                           count_ptr: int, keep_ptr: int = 0):
+        """The filter over n device float4 points: kept points (input order) to out_ptr, their
+        count to count_ptr (u32), optionally a u8 keep flag per input point to keep_ptr."""
+        self._check(self._lib.gdf_radius_filter_points(
+            self._h, C.c_void_p(in_ptr), n, C.byref(params), C.c_void_p(out_ptr),
+            C.c_void_p(count_ptr), C.c_void_p(keep_ptr) if keep_ptr else None))
+
+    def radiusFilter(self, lower, upper, radius, min_neighbors, source="voxelized"):
+        """radiusFilter(min, max, radius, minNeighbors) (component.cpp:414-421) on this frame's
+        voxelized cloud (or source="points": its compacted points)."""
+        src = {"points": RF_POINTS, "voxelized": RF_VOXELIZED}[source]
+        p = radius_filter_params(lower, upper, radius, max(int(min_neighbors), 0))
+        self._check(self._lib.gdf_radius_filter(self._h, src, C.byref(p)))
+
+    def setRadiusFilter(self, enable, lower=(-1, -1, -1), upper=(1, 1, 1), radius=0.05,
+                        min_neighbors=1):
+        """Arm (sticky) or disarm the filter at the end of every single frame's processFrame."""
+        p = radius_filter_params(lower, upper, radius, max(int(min_neighbors), 0))
+        self._check(self._lib.gdf_set_radius_filter(self._h, 1 if enable else 0, C.byref(p)))
+
+    def filtered_count(self) -> int:
+        cnt = C.c_uint32()
+        self._check(self._lib.gdf_get_filtered_count(self._h, C.byref(cnt)))
+        return cnt.value
+
+    def downloadFilteredPoints(self) -> np.ndarray:
+        """m_points_filtered of this frame (waits for the engine's stream)."""
+        n = self.filtered_count()
+        out = np.empty((max(n, 1), 4), np.float32)
+        cnt = C.c_uint32()
+        self._check(self._lib.gdf_download_filtered_points(self._h, _ptr(out), out.shape[0],
+                                                           C.byref(cnt)))
+        return out[:cnt.value]
+
+    def device_filtered(self):
+        """(device pointer of the filtered float4 points, device pointer of their u32 count)."""
+        p, c = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.gdf_get_device_filtered(self._h, C.byref(p), C.byref(c)))
+        return p.value, c.value
 
     # ---- multi-frame batches ----
     def nextFrameInBatch(self):
