@@ -70,6 +70,59 @@ int gdf_download_filtered_points(gdf_engine* engine, float* out_xyzw, uint32_t c
                                  uint32_t* out_count);
 int gdf_get_device_filtered(gdf_engine* engine, const float** points, const uint32_t** count_device);
 
+/* ---- the filter per segment (per frame of a batch), over a sparse cell table -----------------
+ *
+ * For segments [start[s], start[s + 1]), s < nseg, of an array of float4 points the result for
+ * segment s is exactly the rule above applied to that segment alone: a point of another segment
+ * is nobody's neighbour.  The output is the kept points of all segments back to back, in segment
+ * order and then input order, all four words bit for bit.  The cells live in a hashed table keyed
+ * by segment and cell, sized by the points; it never changes a bit of the result.
+ *
+ * The sparse cell plan: the per-axis rule and the guards of gdf_radius_filter_plan (cells =
+ * max(1, floor((upper - lower) / (radius (1 + 2^-10)))) capped at 1024, one cell in all for
+ * r2 < 2^-100, one cell on an axis longer than 2^100) with no cap on the product.  The argument
+ * checks are the same. */
+int gdf_radius_filter_plan_sparse(const gdf_radius_filter_params* params, uint32_t cells[3],
+                                  float edge[3]);
+
+/* The segmented filter over device memory.  seg_start_device holds nseg + 1 u32 words, 1 <= nseg
+ * <= 64; the starts are clamped to n_cap and made non-decreasing on read, and the table and the
+ * points must not change while the call is in flight.  Kept points go to out_points_device
+ * (capacity n_cap), out_seg_start_device[s] (nseg + 1 words) is the number of kept points before
+ * start[s] - [0] = 0, [nseg] = the total, which also goes to out_count_device.  keep_device !=
+ * NULL: a u8 keep flag per input point i < start[nseg]; bytes behind that are left untouched and
+ * the points there are not read.  GDF_ERR_ARG for nseg outside 1..64, in == out, n_cap above 2^30
+ * and bad params; n_cap = 0 is valid. */
+int gdf_radius_filter_segments(gdf_engine* engine, const float* in_points_device, uint32_t n_cap,
+                               const uint32_t* seg_start_device, uint32_t nseg,
+                               const gdf_radius_filter_params* params, float* out_points_device,
+                               uint32_t* out_seg_start_device, uint32_t* out_count_device,
+                               uint8_t* keep_device);
+
+/* Stage call on the addressed slot's frame or batch, one segment per frame: GDF_RF_POINTS takes the
+ * device point ranges of the batch, GDF_RF_VOXELIZED its voxel ranges; a single frame is the one
+ * segment {0, count}, the count read on the device.  GDF_ERR_STATE before that stage and for a
+ * frame armed with the emit partition. */
+int gdf_radius_filter_batch(gdf_engine* engine, int source, const gdf_radius_filter_params* params);
+
+/* Armed (sticky until disabled), for multi-frame batches only: a batch's gdf_process_frame ends
+ * with the segmented filter, on the slot's stream, outside the captured graph; the source is chosen
+ * as gdf_set_radius_filter chooses it.  A deferred-voxelize batch processed while armed fails with
+ * GDF_ERR_STATE before any launch.  Single frames stay governed by gdf_set_radius_filter alone, and
+ * a batch processed with only that arm set still fails with GDF_ERR_STATE. */
+int gdf_set_radius_filter_batch(gdf_engine* engine, int enable,
+                                const gdf_radius_filter_params* params);
+
+/* The ranges of the addressed slot's filtered result: filtered_start[f] is the first filtered point
+ * of frame f, nframes + 1 entries ([nframes] = the count; {0, count} after a single-cloud filter).
+ * filtered_start may be NULL to ask for out_frames alone.  gdf_get_filtered_count,
+ * gdf_download_filtered_points and gdf_get_device_filtered serve the concatenated result. */
+int gdf_get_filtered_ranges(gdf_engine* engine, uint32_t* filtered_start, uint32_t capacity,
+                            uint32_t* out_frames);
+/* ... the same table on the device (nseg + 1 words); GDF_ERR_STATE unless the slot's last filter
+ * was a segmented one. */
+int gdf_get_device_filtered_ranges(gdf_engine* engine, const uint32_t** start_device, uint32_t* nseg);
+
 #ifdef __cplusplus
 }
 #endif

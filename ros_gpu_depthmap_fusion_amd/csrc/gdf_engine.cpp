@@ -406,6 +406,12 @@ struct Slot {
         bool cnt_dirty = false;     // a failed call may have left cell counters set: cleared first
         bool valid = false;         // a filter ran on this slot's frame (until its next gdf_clear)
         uint32_t cap = 0;           // points the results can hold (the source's capacity)
+        // the segmented filter's sparse cell table (it shares the buffers above; its counters are
+        // `cnt`, zero between calls like the dense grid's) and the ranges of a batch's result
+        DevBuf keys;                // all ones (empty) between calls
+        bool keys_dirty = false;    // a failed call may have left keys set: cleared first
+        DevBuf seg_out;             // kept points before each frame of the batch [nseg + 1]
+        uint32_t nseg = 0;          // segments of seg_out (0: the result is one cloud's)
     } rf;
     bool frame_pts = false, frame_vox = false;  // compaction / voxelize launched since gdf_clear
     bool frame_parts = false;       // ... for a frame armed with the emit partition
@@ -565,6 +571,9 @@ struct gdf_engine {
     // gdf_set_radius_filter: single frames of gdf_process_frame end with the filter (sticky)
     bool rf_armed = false;
     gdf_radius_filter_params rf_params{};
+    // gdf_set_radius_filter_batch: multi-frame batches end with the segmented filter (sticky)
+    bool rfb_armed = false;
+    gdf_radius_filter_params rfb_params{};
     bool emit_part = true;  // GDF_NO_EMIT_PART (else: compaction, then the partition pass)
     // a frame armed with gdf_set_emit_partition sets its occupancy marks (gdf_set_partition_marks:
     // off when the caller builds the union from the key-range voxelize, gdf_voxelize_runs_marked)
@@ -2229,7 +2238,114 @@ void radius_filter_stage(gdf_engine* e, int source, const gdf_radius_filter_para
     q.rf.out.ensure((size_t)std::max<uint32_t>(cap, 1u) * 16);
     q.rf.count.ensure(256);
     q.rf.cap = cap;
+    q.rf.nseg = 0;  // (one cloud: no ranges of a batch)
     radius_filter_run(e, in, n_dev, cap, p, q.rf.out.as<float4>(), q.rf.count.as<uint32_t>(), nullptr);
+    q.rf.valid = true;
+}
+
+// The segmented filter over the sparse cell table: segments from seg_start (device, nseg + 1), or -
+// seg_start == nullptr - the one segment [0, min(*n_dev, n_cap)).  keep == nullptr: the slot's own
+// flags.
+void radius_segments_run(gdf_engine* e, const float4* in, uint32_t n_cap, const uint32_t* seg_start,
+                         const uint32_t* n_dev, uint32_t nseg, const gdf_radius_filter_params* p,
+                         float4* out, uint32_t* out_start, uint32_t* out_count, uint8_t* keep) {
+    RadiusPlan pl;
+    if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    if (nseg < 1 || nseg > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: 1..64 segments");
+    if (n_cap > kRfMaxSegPoints) fail(GDF_ERR_ARG, "radius filter: more than 2^30 points");
+    Slot::Filter& w = e->sl().rf;
+    hipStream_t st = e->s();
+    const size_t nb = std::max<uint32_t>(n_cap, 1u);
+    const uint32_t nt = std::max<uint32_t>(rf_tiles(n_cap), 1u);
+    const uint32_t H = rf_table_slots(n_cap);
+    w.cell.ensure(nb * 4);
+    w.rank.ensure(nb * 4);
+    w.sorted.ensure(nb * 16);
+    w.scell.ensure(nb * 4);
+    if (!keep) w.keep.ensure(nb);
+    w.start.ensure(((size_t)H + 1) * 4);
+    w.cell_sums.ensure(rf_scan_words(H) * 4);
+    w.tile_cnt.ensure(((size_t)nt + 1) * 4);
+    w.tile_off.ensure(((size_t)nt + 1) * 4);
+    w.tile_sums.ensure(rf_scan_words(nt) * 4);
+    // counters zero and keys empty between calls (the scan zeroes the counters, the compaction
+    // empties the slots it filled); a grown buffer, or one a failed call may have left set, is
+    // cleared whole
+    if (!w.cnt.ensure_zero(((size_t)H + 1) * 4, st) && w.cnt_dirty)
+        HIPCHK(hipMemsetAsync(w.cnt.p, 0, w.cnt.bytes, st));
+    if (w.keys.ensure((size_t)H * 8) || w.keys_dirty)
+        HIPCHK(hipMemsetAsync(w.keys.p, 0xFF, w.keys.bytes, st));
+    RadiusSegArgs a{};
+    a.in = in;
+    a.n_cap = n_cap;
+    a.seg_start = seg_start;
+    a.n_dev = n_dev;
+    a.nseg = nseg;
+    for (int k = 0; k < 3; ++k) {
+        a.lo[k] = p->lower[k];
+        a.hi[k] = p->upper[k];
+        a.inv[k] = pl.inv[k];
+        a.cells[k] = pl.cells[k];
+    }
+    a.r2 = pl.r2;
+    a.min_neighbors = p->min_neighbors;
+    a.nslots = H;
+    a.keys = w.keys.as<uint64_t>();
+    a.cnt = w.cnt.as<uint32_t>();
+    a.start = w.start.as<uint32_t>();
+    a.cell_sums = w.cell_sums.as<uint32_t>();
+    a.slot = w.cell.as<uint32_t>();
+    a.rank = w.rank.as<uint32_t>();
+    a.sorted = w.sorted.as<float4>();
+    a.sslot = w.scell.as<uint32_t>();
+    a.keep = keep ? keep : w.keep.as<uint8_t>();
+    a.tile_cnt = w.tile_cnt.as<uint32_t>();
+    a.tile_off = w.tile_off.as<uint32_t>();
+    a.tile_sums = w.tile_sums.as<uint32_t>();
+    a.out = out;
+    a.out_start = out_start;
+    a.out_count = out_count;
+    w.cnt_dirty = w.keys_dirty = true;
+    HIPCHK(launch_radius_filter_segments(a, st));
+    w.cnt_dirty = w.keys_dirty = false;
+}
+
+// the stage call for a frame or a batch: one segment per frame, the ranges read on the device
+void radius_filter_batch_stage(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
+    Slot& q = e->sl();
+    if (source != GDF_RF_POINTS && source != GDF_RF_VOXELIZED) fail(GDF_ERR_ARG, "radius filter: bad source");
+    if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "radius filter before the frame's compaction");
+    if (q.frame_parts)
+        fail(GDF_ERR_STATE, "radius filter: not for a frame armed with the emit partition");
+    const bool batch = q.nframes > 1;
+    if (q.nframes > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: more than 64 frames");
+    const float4* in;
+    const uint32_t *n_dev, *seg_start;
+    uint32_t cap;
+    if (source == GDF_RF_VOXELIZED) {
+        if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "radius filter before the frame's voxelize");
+        in = q.d_vox.as<float4>();
+        n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
+        seg_start = q.d_fvox.as<uint32_t>();
+        cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, kRfMaxSegPoints);
+    } else {
+        in = q.d_pts.as<float4>();
+        n_dev = q.d_misc.as<uint32_t>() + kCount;
+        seg_start = q.d_fstart.as<uint32_t>();
+        cap = q.n_total;
+    }
+    if (batch && !seg_start) fail(GDF_ERR_STATE, "radius filter: the batch has no frame ranges");
+    RadiusPlan pl;
+    if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    q.rf.valid = false;
+    q.rf.out.ensure((size_t)std::max<uint32_t>(cap, 1u) * 16);
+    q.rf.count.ensure(256);
+    q.rf.seg_out.ensure((kRfMaxSegs + 1) * 4);
+    q.rf.cap = cap;
+    q.rf.nseg = q.nframes;
+    radius_segments_run(e, in, cap, batch ? seg_start : nullptr, batch ? nullptr : n_dev, q.nframes, p,
+                        q.rf.out.as<float4>(), q.rf.seg_out.as<uint32_t>(), q.rf.count.as<uint32_t>(),
+                        nullptr);
     q.rf.valid = true;
 }
 
@@ -2914,11 +3030,16 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
                                     "(gdf_take_occupancy_marks + gdf_voxel_occupancy_grid_batch)");
             if (e->nframes > kMaxCams) fail(GDF_ERR_ARG, "at most 16 frames per batch");
         }
-        if (e->rf_armed) {  // (before anything is launched)
+        // (before anything is launched)  Batches are governed by the batch arm, single frames by
+        // the single-frame arm; a batch under the single-frame arm alone is refused as ever
+        const bool rf_batch = e->nframes > 1 && e->rfb_armed;
+        if (e->rf_armed && !rf_batch) {
             if (e->nframes > 1) fail(GDF_ERR_STATE, "radius filter armed: not for a multi-frame batch");
             if (p->enable_voxel_filter && p->defer_voxelize)
                 fail(GDF_ERR_STATE, "radius filter armed: not for a deferred-voxelize frame");
         }
+        if (rf_batch && p->enable_voxel_filter && p->defer_voxelize)
+            fail(GDF_ERR_STATE, "radius filter armed: not for a deferred-voxelize batch");
         res.processed = 1;
         upload_point_sequences(e);
         e->ps_filter_set = true;
@@ -2976,7 +3097,10 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
         } else {
             run_frame(e, false);
         }
-        if (e->rf_armed)  // after the frame's chain, outside its captured graph
+        if (rf_batch)  // after the batch's chain, outside its captured graph
+            radius_filter_batch_stage(e, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
+                                      &e->rfb_params);
+        else if (e->rf_armed)  // after the frame's chain, outside its captured graph
             radius_filter_stage(e, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
                                 &e->rf_params);
         res.num_depth_points = e->depth_total;
@@ -3052,6 +3176,74 @@ int gdf_set_radius_filter(gdf_engine* e, int enable, const gdf_radius_filter_par
             e->rf_params = *p;
         }
         e->rf_armed = enable != 0;
+    });
+}
+
+int gdf_radius_filter_segments(gdf_engine* e, const float* in, uint32_t n_cap,
+                               const uint32_t* seg_start, uint32_t nseg,
+                               const gdf_radius_filter_params* p, float* out, uint32_t* out_seg_start,
+                               uint32_t* out_count, uint8_t* keep) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (!p || !seg_start || !out_seg_start || !out_count || (n_cap && (!in || !out)))
+            fail(GDF_ERR_ARG, "radius filter: null argument");
+        if (nseg < 1 || nseg > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: 1..64 segments");
+        if (n_cap && in == out) fail(GDF_ERR_ARG, "radius filter: in-place is not supported");
+        radius_segments_run(e, reinterpret_cast<const float4*>(in), n_cap, seg_start, nullptr, nseg, p,
+                            reinterpret_cast<float4*>(out), out_seg_start, out_count, keep);
+    });
+}
+
+int gdf_radius_filter_batch(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (!p) fail(GDF_ERR_ARG, "radius filter: null parameters");
+        radius_filter_batch_stage(e, source, p);
+    });
+}
+
+int gdf_set_radius_filter_batch(gdf_engine* e, int enable, const gdf_radius_filter_params* p) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        if (enable) {
+            RadiusPlan pl;
+            if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+            e->rfb_params = *p;
+        }
+        e->rfb_armed = enable != 0;
+    });
+}
+
+int gdf_get_filtered_ranges(gdf_engine* e, uint32_t* filtered_start, uint32_t capacity,
+                            uint32_t* out_frames) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (!q.rf.valid) fail(GDF_ERR_STATE, "no radius filter ran on this frame");
+        const uint32_t nf = std::max<uint32_t>(q.rf.nseg, 1u);
+        if (out_frames) *out_frames = nf;
+        if (!filtered_start) return;
+        if (capacity < nf + 1) fail(GDF_ERR_CAPACITY, "filtered ranges: need nframes + 1 entries");
+        if (q.rf.nseg == 0) {  // one cloud's result
+            filtered_start[0] = 0;
+            filtered_start[1] = filtered_count(e);
+            return;
+        }
+        HIPCHK(hipMemcpyAsync(filtered_start, q.rf.seg_out.p, (size_t)(nf + 1) * 4,
+                              hipMemcpyDeviceToHost, e->s()));
+        e->sync();
+        for (uint32_t k = 0; k <= nf; ++k) filtered_start[k] = std::min(filtered_start[k], q.rf.cap);
+    });
+}
+
+int gdf_get_device_filtered_ranges(gdf_engine* e, const uint32_t** start_device, uint32_t* nseg) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (!q.rf.valid || q.rf.nseg == 0)
+            fail(GDF_ERR_STATE, "no segmented radius filter ran on this frame");
+        if (start_device) *start_device = q.rf.seg_out.as<const uint32_t>();
+        if (nseg) *nseg = q.rf.nseg;
     });
 }
 

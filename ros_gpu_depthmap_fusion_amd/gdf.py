@@ -175,6 +175,9 @@ EXPORTED = [
     "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
     "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
     "gdf_get_device_filtered",
+    # ... per segment (per frame of a batch), over the sparse cell table
+    "gdf_radius_filter_plan_sparse", "gdf_radius_filter_segments", "gdf_radius_filter_batch",
+    "gdf_set_radius_filter_batch", "gdf_get_filtered_ranges", "gdf_get_device_filtered_ranges",
 ]
 
 
@@ -313,6 +316,13 @@ def load_library(path: str = LIB_PATH):
         "gdf_get_filtered_count": (i32, [vp, P(u32)]),
         "gdf_download_filtered_points": (i32, [vp, vp, u32, P(u32)]),
         "gdf_get_device_filtered": (i32, [vp, P(vp), P(vp)]),
+        "gdf_radius_filter_plan_sparse": (i32, [P(RadiusFilterParams), vp, vp]),
+        "gdf_radius_filter_segments": (i32, [vp, vp, u32, vp, u32, P(RadiusFilterParams), vp, vp, vp,
+                                             vp]),
+        "gdf_radius_filter_batch": (i32, [vp, i32, P(RadiusFilterParams)]),
+        "gdf_set_radius_filter_batch": (i32, [vp, i32, P(RadiusFilterParams)]),
+        "gdf_get_filtered_ranges": (i32, [vp, vp, u32, P(u32)]),
+        "gdf_get_device_filtered_ranges": (i32, [vp, P(vp), P(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -364,6 +374,19 @@ def radius_filter_plan(lower, upper, radius, min_neighbors=0):
     cells = np.zeros(3, np.uint32)
     edge = np.zeros(3, np.float32)
     rc = lib.gdf_radius_filter_plan(C.byref(p), _ptr(cells), _ptr(edge))
+    if rc != GDF_OK:
+        raise GDFError(rc, lib.gdf_last_error().decode())
+    return tuple(int(c) for c in cells), edge
+
+
+def radius_filter_plan_sparse(lower, upper, radius, min_neighbors=0):
+    """The segmented filter's cell plan (gdf_radius_filter_plan_sparse): as radius_filter_plan,
+    with no cap on the product of the axes."""
+    lib = load_library()
+    p = radius_filter_params(lower, upper, radius, min_neighbors)
+    cells = np.zeros(3, np.uint32)
+    edge = np.zeros(3, np.float32)
+    rc = lib.gdf_radius_filter_plan_sparse(C.byref(p), _ptr(cells), _ptr(edge))
     if rc != GDF_OK:
         raise GDFError(rc, lib.gdf_last_error().decode())
     return tuple(int(c) for c in cells), edge
@@ -933,6 +956,47 @@ class GPUDepthmapFusion:
         """Arm (sticky) or disarm the filter at the end of every single frame's processFrame."""
         p = radius_filter_params(lower, upper, radius, max(int(min_neighbors), 0))
         self._check(self._lib.gdf_set_radius_filter(self._h, 1 if enable else 0, C.byref(p)))
+
+    def radiusFilterSegments(self, in_ptr: int, n_cap: int, seg_start_ptr: int, nseg: int,
+                             params: RadiusFilterParams, out_ptr: int, out_seg_start_ptr: int,
+                             count_ptr: int, keep_ptr: int = 0):
+        """The filter per segment [start[s], start[s + 1]) of n_cap device float4 points (start:
+        nseg + 1 device u32): kept points of all segments back to back to out_ptr, the kept points
+        before each segment to out_seg_start_ptr (nseg + 1 u32), the total to count_ptr,
+        optionally a u8 keep flag per input point below start[nseg] to keep_ptr."""
+        self._check(self._lib.gdf_radius_filter_segments(
+            self._h, C.c_void_p(in_ptr), n_cap, C.c_void_p(seg_start_ptr), nseg, C.byref(params),
+            C.c_void_p(out_ptr), C.c_void_p(out_seg_start_ptr), C.c_void_p(count_ptr),
+            C.c_void_p(keep_ptr) if keep_ptr else None))
+
+    def radiusFilterBatch(self, lower, upper, radius, min_neighbors, source="voxelized"):
+        """radiusFilter on every frame of this batch (or this frame), one launch chain: each
+        frame's voxelized cloud (or source="points") filtered on its own."""
+        src = {"points": RF_POINTS, "voxelized": RF_VOXELIZED}[source]
+        p = radius_filter_params(lower, upper, radius, max(int(min_neighbors), 0))
+        self._check(self._lib.gdf_radius_filter_batch(self._h, src, C.byref(p)))
+
+    def setRadiusFilterBatch(self, enable, lower=(-1, -1, -1), upper=(1, 1, 1), radius=0.05,
+                             min_neighbors=1):
+        """Arm (sticky) or disarm the per-frame filter at the end of every multi-frame batch's
+        processFrame (single frames stay with setRadiusFilter)."""
+        p = radius_filter_params(lower, upper, radius, max(int(min_neighbors), 0))
+        self._check(self._lib.gdf_set_radius_filter_batch(self._h, 1 if enable else 0, C.byref(p)))
+
+    def filtered_ranges(self) -> np.ndarray:
+        """filtered_start, nframes + 1 entries: frame f's filtered points are
+        downloadFilteredPoints()[filtered_start[f]:filtered_start[f + 1]]."""
+        nf = C.c_uint32()
+        self._check(self._lib.gdf_get_filtered_ranges(self._h, None, 0, C.byref(nf)))
+        fs = np.zeros(nf.value + 1, np.uint32)
+        self._check(self._lib.gdf_get_filtered_ranges(self._h, _ptr(fs), nf.value + 1, C.byref(nf)))
+        return fs
+
+    def device_filtered_ranges(self):
+        """(device pointer of filtered_start, its number of segments) of a segmented filter."""
+        p, n = C.c_void_p(), C.c_uint32()
+        self._check(self._lib.gdf_get_device_filtered_ranges(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def filtered_count(self) -> int:
         cnt = C.c_uint32()

@@ -13,7 +13,14 @@ frame_us (the median of the same frame's gdf_process_frame chain, timed the same
 process), the candidate pairs the cell grid offers (host count from the plan), the count kernel's
 time taken as the call's time minus the min_neighbors = 0 call's (which skips the candidate loops
 and is otherwise the same passes), pairs per second where that is exact (noexit), and the bytes the
-other passes move (model of DESIGN.md §11)."""
+other passes move (model of DESIGN.md §11).
+
+    python tools/radius_bench.py --batch 8 [--tables a,b] [--sources points,voxelized] [--mins 0,4,16]
+
+measures the filter per frame of a batch instead (profiles/radius_filter_batch/):
+table a, a batch of 8 dense VGA frames - one gdf_radius_filter_batch call against eight
+gdf_radius_filter_points calls on the same segments, next to the batch's own chain; table b, the
+clouds above as one segment over the sparse cell table against the dense grid's call."""
 import argparse
 import ctypes as C
 import json
@@ -79,18 +86,122 @@ def offered_pairs(pts, lower, upper, radius):
     return len(p), int((occ * near).sum() - len(p)), cells
 
 
+def emit(lines, line):
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+
+
+def batch_lines(a, p, lower, upper, radius, lines):
+    """(a) A batch of `--batch` dense VGA frames (one camera, as bench.py's step): the segmented
+    call (gdf_radius_filter_batch) against one gdf_radius_filter_points call per frame on the same
+    segments, next to the batch's own chain.  us: all launches of the call(s), median."""
+    from ros_gpu_depthmap_fusion_amd.gdf import radius_filter_params
+    W, H = SIZES["vga"]
+    B = a.batch
+    gpu = GPUDepthmapFusion(0)
+    cam = synth.make_camera(0, W, H)
+    depths = [hiprt.DeviceArray.from_numpy(synth.dense_frame(cam, 0, f)) for f in range(B)]
+    pc = p.to_c(synchronous=False)
+
+    def chain():
+        gpu.clear()
+        for j, d in enumerate(depths):
+            if j:
+                gpu.nextFrameInBatch()
+            gpu.addDepthmapDevice(d.ptr, W, H, *cam.intrinsics(), cam.T_world, cam.T_crop)
+        gpu.processFramePrepared(pc)
+
+    timer = Timer(gpu.stream())
+    chain_us, _ = median_us(timer, chain, a.calls, a.warmup)
+    gpu.synchronize()
+    ps, vs = gpu.batch_ranges()
+    for source, pts, starts in (("voxelized", gpu.downloadVoxelizedPoints(), vs),
+                                ("points", gpu.downloadPoints(), ps)):
+        if source not in a.sources.split(","):
+            continue
+        n = len(pts)
+        d_in = hiprt.DeviceArray.from_numpy(np.ascontiguousarray(pts, np.float32))
+        d_out, d_cnt = hiprt.DeviceArray(16 * max(n, 1)), hiprt.DeviceArray(4 * B)
+        for m in a.min_list:
+            prm = radius_filter_params(lower, upper, radius, m)
+
+            def per_frame():
+                for s in range(B):
+                    b, e = int(starts[s]), int(starts[s + 1])
+                    gpu.radiusFilterPoints(d_in.ptr + 16 * b, e - b, prm, d_out.ptr + 16 * b,
+                                           d_cnt.ptr + 4 * s)
+
+            seg_us, calls = median_us(
+                timer, lambda: gpu.radiusFilterBatch(lower, upper, radius, m, source=source),
+                a.calls, a.warmup)
+            kept = gpu.filtered_count()
+            pf_us, _ = median_us(timer, per_frame, a.calls, a.warmup)
+            gpu.synchronize()
+            kept_pf = int(d_cnt.to_numpy(np.uint32, B).sum())
+            emit(lines, dict(table="a", cloud=f"vga_b{B}_{source}", frames=B, n=n, kept=kept,
+                             kept_per_frame_calls=kept_pf, min_neighbors=m,
+                             segments_us=round(seg_us, 2), per_frame_calls_us=round(pf_us, 2),
+                             chain_us=round(chain_us, 2), calls=calls,
+                             ratio=round(pf_us / seg_us, 3)))
+    gpu.close()
+
+
+def single_lines(a, p, lower, upper, radius, lines):
+    """(b) The rows of the single-cloud table: nseg = 1 over the sparse table (gdf_radius_filter_batch
+    on a single frame) against the dense grid's call (gdf_radius_filter) on the same input."""
+    for size in a.sizes.split(","):
+        W, H = SIZES[size]
+        gpu = GPUDepthmapFusion(0)
+        cam = synth.make_camera(0, W, H)
+        depth = hiprt.DeviceArray.from_numpy(synth.dense_frame(cam, 0, 0))
+        gpu.clear()
+        gpu.addDepthmapDevice(depth.ptr, W, H, *cam.intrinsics(), cam.T_world, cam.T_crop)
+        gpu.processFramePrepared(p.to_c(synchronous=False))
+        gpu.synchronize()
+        timer = Timer(gpu.stream())
+        counts = {"points": len(gpu.downloadPoints()), "voxelized": len(gpu.downloadVoxelizedPoints())}
+        for source in (("points", "voxelized") if size == "vga" else ("points",)):
+            if source not in a.sources.split(","):
+                continue
+            for m in a.min_list:
+                dense_us, calls = median_us(
+                    timer, lambda: gpu.radiusFilter(lower, upper, radius, m, source=source),
+                    a.calls, a.warmup)
+                kept_dense = gpu.filtered_count()
+                sparse_us, _ = median_us(
+                    timer, lambda: gpu.radiusFilterBatch(lower, upper, radius, m, source=source),
+                    a.calls, a.warmup)
+                kept = gpu.filtered_count()
+                emit(lines, dict(table="b", cloud=f"{size}_{source}", n=counts[source], kept=kept,
+                                 kept_dense=kept_dense, min_neighbors=m, sparse_us=round(sparse_us, 2),
+                                 dense_us=round(dense_us, 2), calls=calls,
+                                 ratio=round(dense_us / sparse_us, 3)))
+        gpu.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--sizes", default="vga,4k")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="N > 0: the segmented filter's tables instead (a batch of N VGA frames "
+                         "against per-frame calls; one segment against the dense call)")
+    ap.add_argument("--tables", default="a,b", help="with --batch: which of its two tables")
+    ap.add_argument("--sources", default="points,voxelized", help="with --batch: which clouds")
+    ap.add_argument("--mins", default="0,4,16", help="with --batch: min_neighbors values")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    a.min_list = [int(m) for m in a.mins.split(",")]
     build_library()
     p = ComponentParams()
     lower, upper, radius = tuple(p.voxel_min), tuple(p.voxel_max), 0.05
     lines = []
-    for size in a.sizes.split(","):
+    if a.batch > 0 and "a" in a.tables.split(","):
+        batch_lines(a, p, lower, upper, radius, lines)
+    if a.batch > 0 and "b" in a.tables.split(","):
+        single_lines(a, p, lower, upper, radius, lines)
+    for size in ([] if a.batch > 0 else a.sizes.split(",")):
         W, H = SIZES[size]
         gpu = GPUDepthmapFusion(0)
         cam = synth.make_camera(0, W, H)
