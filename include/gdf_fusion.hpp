@@ -415,6 +415,27 @@ public:
         mergeLabelsAcrossLayers();
         createCCObjects();
     }
+    // The frame's points by object (no reference counterpart; include/gdf_segment.h, "object id
+    // per point"): after objectSegmentation(), the object id of every point of m_points, the
+    // points of every object with at least max(min_voxels, 1) voxels grouped by object (object o's
+    // at [m_objectPointStarts[o], m_objectPointStarts[o + 1]) in m_points order), each grouped
+    // point's index into m_points, and the objects' voxel counts - computed on the GPU.
+    void objectPoints(uint32_t min_voxels = 0) {
+        if (!seg_) throw std::runtime_error("objectPoints before objectSegmentation");
+        check(gdf_seg_object_points(seg_, h_, min_voxels));
+        uint32_t nobj = 0, total = 0, n = 0;
+        check(gdf_seg_get_object_points(seg_, &nobj, &total));
+        check(gdf_seg_get_object_points_input(seg_, &n));
+        m_pointObjectIds.resize(n);
+        m_points_objects.resize(total);
+        m_objectPointIndex.resize(total);
+        m_objectPointStarts.resize((size_t)nobj + 1);
+        m_objectVoxels.resize(nobj);
+        check(gdf_seg_download_object_points(
+            seg_, m_pointObjectIds.data(), n, reinterpret_cast<float*>(m_points_objects.data()),
+            m_objectPointIndex.data(), total, m_objectPointStarts.data(), m_objectVoxels.data(),
+            nobj + 1));
+    }
     // objectTracking (:2727-2944): associates m_ccObjects with m_ccObjectTracks
     void objectTracking(float min_area) { object_tracking(m_ccObjects, m_ccObjectTracks, min_area); }
 
@@ -463,6 +484,11 @@ public:
     std::vector<CCObjectTrack> m_ccObjectTracks;  // (gpu_depthmap_fusion.h:343)
     std::vector<gdf_cc_object> m_ccObjectRecords;  // the GPU's aggregates behind m_ccObjects
     std::vector<uint32_t> m_ccObjectComponents;
+    // objectPoints: ids per point of m_points (GDF_OBJ_NONE: in no object), the kept points grouped
+    // by object, their indices into m_points, the objects' ranges and voxel counts
+    std::vector<uint32_t> m_pointObjectIds;
+    std::vector<vec4> m_points_objects;
+    std::vector<uint32_t> m_objectPointIndex, m_objectPointStarts, m_objectVoxels;
 
 private:
     // one CCObject from the GPU record + the contours (fusion.cpp:2371-2537)

@@ -105,6 +105,75 @@ int gdf_seg_create_objects(gdf_segmenter* seg, const float lower[3], const float
 int gdf_seg_get_device_results(gdf_segmenter* seg, const uint16_t** labels, const int32_t** stats5,
                                const double** centroids2, const uint8_t** connections);
 
+/* ---- object id per point and the points grouped by object ---------------------
+ *
+ * No reference counterpart; the rule is this library's specification.  With W, H, L the labelled
+ * grid, lstart[z] = sum(num_labels[< z]), merged / nobj as gdf_seg_merge_labels gives them:
+ *   id      c = cells[i] (x + y W + z W H, as computeVoxelCoords writes it); c >= W H L or
+ *           labels[c] == 0 (a background cell): GDF_OBJ_NONE; else merged[lstart[c / (W H)] + labels[c]]
+ *   voxels  voxels[o] = sum of stats[k][AREA] over the foreground labels k with merged[k] == o
+ *           (a label is foreground unless k == lstart[z] for some z; a background object has 0)
+ *   keep    keep[o] = voxels[o] >= max(min_voxels, 1); a point is kept iff id < nobj and keep[id]
+ *   output  ids[n] in input order (independent of keep); the kept points partitioned by object,
+ *           object o's at [obj_start[o], obj_start[o + 1]) in input order, all four words bit for
+ *           bit; obj_start[0] = 0, obj_start[nobj] = the kept total (also a device count word);
+ *           index[j] = the input index of output point j; voxels[nobj]
+ * Integer gathers, integer adds and a stable partition: the result is exact.  Everything is
+ * enqueued with no host wait, except that the first call after a labelling waits once for nobj
+ * (as gdf_seg_merge_labels does) and that a workspace buffer that has to grow is reallocated
+ * (the workspace is grow-only: a steady stream of frames stops growing).  The input count may be
+ * a device word (count_device != NULL: n = min(*count_device, n_cap)); rows at and beyond n are
+ * neither read nor written.  Results stay valid until the next gdf_seg_label_* or the next
+ * gdf_seg_group_points / gdf_seg_object_points.
+ * Streams: the labelling and these calls may run on different streams (the segmenter's and an
+ * engine's), in any order; a call whose stream differs from the previous call's waits on the
+ * device for that call's work, so no host wait is needed between them. */
+#define GDF_OBJ_NONE 0xFFFFFFFFu
+
+/* ids alone, on any device arrays, on the segmenter's stream; needs a labelling with
+ * GDF_SEG_CONNECTIONS (GDF_ERR_STATE) */
+int gdf_seg_point_object_ids(gdf_segmenter* seg, const uint32_t* cells_device, uint32_t n_cap,
+                             const uint32_t* count_device, uint32_t* ids_out_device);
+
+/* the partition alone, on any (points, ids), on the segmenter's stream: keep_device u8[nobj] or
+ * NULL (keep all); ids >= nobj are dropped.  Independent of the labelling.  GDF_ERR_ARG for null
+ * pointers, nobj == 0 and nobj > 2^24; n_cap == 0 succeeds with empty results. */
+int gdf_seg_group_points(gdf_segmenter* seg, const float* points_device, const uint32_t* ids_device,
+                         uint32_t n_cap, const uint32_t* count_device, uint32_t nobj,
+                         const uint8_t* keep_device);
+
+/* The whole rule on the engine's compacted points, its voxel coords and its device-side count, on
+ * the engine's stream.  GDF_ERR_STATE, before any launch: no labelling or one without
+ * GDF_SEG_CONNECTIONS; W, H, L differ from the engine's grid size; and what
+ * gdf_radius_filter(GDF_RF_POINTS) refuses on the engine's side (before the frame's compaction, a
+ * multi-frame batch, a frame armed with the emit partition); an engine on another device than
+ * the segmenter's.  GDF_ERR_ARG for nobj > 2^24. */
+int gdf_seg_object_points(gdf_segmenter* seg, gdf_engine* engine, uint32_t min_voxels);
+
+/* the object count and the kept total of the last call (waits) */
+int gdf_seg_get_object_points(gdf_segmenter* seg, uint32_t* nobj, uint32_t* total);
+/* the input count n of the last call, i.e. the length of ids (waits); it belongs to that call
+ * and does not follow the engine's later frames */
+int gdf_seg_get_object_points_input(gdf_segmenter* seg, uint32_t* n);
+/* Downloads (wait); every pointer may be NULL.  ids: the n ids of gdf_seg_object_points; points_xyzw
+ * and index: total rows; obj_start: nobj + 1 words; voxels: nobj words.  ids and voxels are
+ * GDF_ERR_STATE after gdf_seg_group_points (it computes neither).  GDF_ERR_CAPACITY when a
+ * capacity (in rows / words; obj_capacity >= nobj + 1) is too small. */
+int gdf_seg_download_object_points(gdf_segmenter* seg, uint32_t* ids, uint32_t ids_capacity,
+                                   float* points_xyzw, uint32_t* index, uint32_t points_capacity,
+                                   uint32_t* obj_start, uint32_t* voxels, uint32_t obj_capacity);
+/* the same on the device; ids and voxels are NULL after gdf_seg_group_points */
+int gdf_seg_get_device_object_points(gdf_segmenter* seg, const uint32_t** ids, const float** points,
+                                     const uint32_t** index, const uint32_t** obj_start,
+                                     const uint32_t** voxels, const uint32_t** count_device);
+/* Instrumentation: with enable != 0 the next group / object-points calls record events around
+ * their passes; gdf_seg_get_object_points_times (waits) then gives the last call's times in
+ * milliseconds: [ids + sizes (0 for gdf_seg_group_points)], per 8-bit pass [count + scan, scatter],
+ * [gather], [starts]: 2 * passes + 3 values. */
+int gdf_seg_set_profiling(gdf_segmenter* seg, int enable);
+int gdf_seg_get_object_points_times(gdf_segmenter* seg, float* ms, uint32_t capacity,
+                                    uint32_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #include "gdf.h"
 #include "gdf_kernels.hpp"
 #include "gdf_filter.hpp"
+#include "gdf_object_points.hpp"
 
 using namespace gdf;
 
@@ -2359,6 +2360,28 @@ uint32_t filtered_count(gdf_engine* e) {
 }
 
 }  // namespace
+
+// the addressed slot's compacted points, voxel coords and device count for the segmenter's
+// object-points stage (gdf_seg_object_points): what gdf_radius_filter(GDF_RF_POINTS) refuses is
+// refused here, for the same reasons
+int gdf::engine_frame_points(gdf_engine* e, FramePoints* out) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (q.nframes > 1 && q.frame_pts) fail(GDF_ERR_STATE, "object points: not for a multi-frame batch");
+        if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "object points before the frame's compaction");
+        if (q.frame_parts)
+            fail(GDF_ERR_STATE, "object points: not for a frame armed with the emit partition");
+        if (!e->grid_set || !q.coords_valid) fail(GDF_ERR_STATE, "object points need the frame's voxel coords");
+        out->pts = q.d_pts.as<float4>();
+        out->coords = q.d_coords.as<uint32_t>();
+        out->n_dev = q.d_misc.as<uint32_t>() + kCount;
+        out->cap = q.n_total;
+        std::memcpy(out->gs, e->gs, 12);
+        out->stream = e->s();
+        out->device = e->device;
+    });
+}
 
 // ==== C-ABI ============================================================================================
 extern "C" {

@@ -36,6 +36,7 @@
 #include "gdf.h"
 #include "gdf_segment.h"
 #include "gdf_kernels.hpp"
+#include "gdf_object_points.hpp"
 
 namespace {
 
@@ -858,8 +859,13 @@ struct gdf_segmenter {
     int device = 0;
     hipStream_t own = nullptr, user = nullptr;
     hipStream_t side = nullptr;  // the contour scan runs here, concurrently with the labelling
-    hipEvent_t ev_ready = nullptr, ev_contours = nullptr;
+    hipEvent_t ev_ready = nullptr, ev_contours = nullptr, ev_last = nullptr;
     hipStream_t s() const { return user ? user : own; }
+    // The stream of the most recent device work on this segmenter's buffers (its own, the
+    // caller's or an engine's) and the event that marks its end: StreamUse orders the next call's
+    // stream after it.
+    hipStream_t last = nullptr;
+    bool last_set = false;
     uint32_t W = 0, H = 0, L = 0, flags = 0;
     bool have = false;
     GpuBuf par, bits, blabel, nlab, lstart, cstart, labels, st, sums, stats5, cent, l2c, conn;
@@ -879,6 +885,21 @@ struct gdf_segmenter {
     std::vector<uint8_t> h_codes;
     uint64_t total_points = 0;
     uint32_t total_contours = 0;
+    // the label merge of this labelling stays on the device (mout: merged[total], then nobj)
+    bool merged_have = false;
+    uint32_t nobj = 0;
+    // object points (gdf_object_points.hip): grow-only workspace and results.  Nothing in it has
+    // to be zero between calls, except voxels, which every call clears before its adds.
+    struct ObjectPoints {
+        GpuBuf ids, pairs0, pairs1, hist, sums, words, out, index, obj_start, voxels, keep;
+        bool valid = false, have_ids = false;  // have_ids: ids and voxels belong to the result
+        bool n_on_device = false;              // words[1] holds n (else n == n_cap)
+        uint32_t nobj = 0, n_cap = 0;
+        hipStream_t stream = nullptr;          // the stream of the last call
+        bool profiling = false;
+        std::vector<hipEvent_t> ev;
+        uint32_t nev = 0;                      // events the last call recorded
+    } op;
 };
 
 namespace {
@@ -899,6 +920,29 @@ int seg_guarded(F&& f) {
         return GDF_ERR_HIP;
     }
 }
+
+// Every call that enqueues work on the segmenter's buffers (labelling, merge, object points)
+// holds one of these for its stream.  The labelling may run on the segmenter's stream and the
+// object-points stage on an engine's, or the other way round, and neither call ends with a host
+// wait: a stream that differs from the previous call's waits for that call's work on the device.
+// One chain of calls, so the order is transitive.
+// The event is recorded when the call ends, failed or not, so the next call needs the event
+// only: the previous stream may be an engine's that is gone by then.
+struct StreamUse {
+    gdf_segmenter* g;
+    hipStream_t s;
+    StreamUse(gdf_segmenter* g_, hipStream_t s_) : g(g_), s(s_) {
+        if (g->last_set && g->last != s) SEGCHK(hipStreamWaitEvent(s, g->ev_last, 0));
+    }
+    ~StreamUse() {
+        if (hipEventRecord(g->ev_last, s) == hipSuccess) {
+            g->last = s;
+            g->last_set = true;
+        }
+    }
+    StreamUse(const StreamUse&) = delete;
+    StreamUse& operator=(const StreamUse&) = delete;
+};
 
 // findContours of every layer on the segmenter's second stream, ordered after the work already
 // on `s` (the grid producer); g->ev_contours marks its end
@@ -958,11 +1002,15 @@ void run_label_layers(gdf_segmenter* g, const uint8_t* grid, uint32_t W, uint32_
                       uint32_t flags, hipStream_t s) {
     g->have = false;  // (a failed call leaves no result behind)
     g->contours_read = false;
+    g->merged_have = false;
+    g->op.valid = false;
     if (!grid || W == 0 || H == 0 || L == 0) seg_fail(GDF_ERR_ARG, "empty grid");
     if (W > 65534 || H > 65534) seg_fail(GDF_ERR_ARG, "layers wider or taller than 65534 cells");
     const uint32_t BW = (W + 1) / 2, BH = (H + 1) / 2;
     const uint64_t nbl = (uint64_t)BW * BH, nb = nbl * L;
     if (nb >= 0xFFFFFFF0ull) seg_fail(GDF_ERR_ARG, "grid too large for 32-bit block indices");
+    // (an object-points call on another stream may still read the previous labelling)
+    StreamUse use(g, s);
     SEGCHK(g->par.ensure(nb * 4));
     SEGCHK(g->bits.ensure(nb));
     SEGCHK(g->blabel.ensure(nb * 4));
@@ -1107,6 +1155,7 @@ int gdf_seg_create(int device, gdf_segmenter** out) {
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_ready, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_contours, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&g->ev_last, hipEventDisableTiming);
         if (e != hipSuccess) {
             delete g;
             SEGCHK(e);
@@ -1124,6 +1173,8 @@ int gdf_seg_destroy(gdf_segmenter* g) {
     if (g->side) (void)hipStreamDestroy(g->side);
     if (g->ev_ready) (void)hipEventDestroy(g->ev_ready);
     if (g->ev_contours) (void)hipEventDestroy(g->ev_contours);
+    if (g->ev_last) (void)hipEventDestroy(g->ev_last);
+    for (hipEvent_t ev : g->op.ev) (void)hipEventDestroy(ev);
     delete g;
     return GDF_OK;
 }
@@ -1278,10 +1329,12 @@ int gdf_seg_download_contours(gdf_segmenter* g, int32_t* l2c, uint32_t* per_laye
 
 namespace {
 
-// mergeLabelsAcrossLayers (fusion.cpp:2243-2361) by k_cc_merge_layers on the segmenter's stream:
-// the connection matrices stay on the device, only the merged ids (4 B per label) come back.
-uint32_t merge_labels(gdf_segmenter* g, uint32_t* merged) {
-    const hipStream_t s = g->s();
+// mergeLabelsAcrossLayers (fusion.cpp:2243-2361) by k_cc_merge_layers: the connection matrices
+// stay on the device, only the merged ids (4 B per label) come back.  The merge runs once per
+// labelling, on the stream of its first user, which waits for the object count; mout keeps
+// merged[total] and nobj on the device for the object-points stage.
+void ensure_merged(gdf_segmenter* g, hipStream_t s) {
+    if (g->merged_have) return;
     const uint32_t T = g->total;
     SEGCHK(g->mgl.ensure((size_t)std::max(T, 1u) * 4));
     SEGCHK(g->mflag.ensure((size_t)std::max(T, 1u) * 4));
@@ -1293,10 +1346,122 @@ uint32_t merge_labels(gdf_segmenter* g, uint32_t* merged) {
                        g->mgl.as<uint32_t>(), g->mflag.as<uint32_t>(), out, out + T);
     SEGCHK(hipGetLastError());
     uint32_t n = 0;
-    if (T) SEGCHK(hipMemcpyAsync(merged, out, (size_t)T * 4, hipMemcpyDeviceToHost, s));
     SEGCHK(hipMemcpyAsync(&n, out + T, 4, hipMemcpyDeviceToHost, s));
     SEGCHK(hipStreamSynchronize(s));
-    return n;
+    g->nobj = n;
+    g->merged_have = true;
+}
+
+uint32_t merge_labels(gdf_segmenter* g, uint32_t* merged) {
+    const hipStream_t s = g->s();
+    StreamUse use(g, s);
+    ensure_merged(g, s);
+    if (g->total) {
+        SEGCHK(hipMemcpyAsync(merged, g->mout.p, (size_t)g->total * 4, hipMemcpyDeviceToHost, s));
+        SEGCHK(hipStreamSynchronize(s));
+    }
+    return g->nobj;
+}
+
+void need_connections(gdf_segmenter* g) {
+    need_result(g);
+    if (!(g->flags & GDF_SEG_CONNECTIONS)) seg_fail(GDF_ERR_STATE, "connections were not requested");
+}
+
+// events of a profiled call: one before the ids and sizes, then launch_object_group's
+hipEvent_t* op_events(gdf_segmenter* g, uint32_t nobj, hipStream_t s) {
+    gdf_segmenter::ObjectPoints& w = g->op;
+    w.nev = 0;
+    if (!w.profiling) return nullptr;
+    const uint32_t need = 2 * gdf::op_passes(nobj) + 4;
+    while (w.ev.size() < need) {
+        hipEvent_t ev;
+        SEGCHK(hipEventCreate(&ev));
+        w.ev.push_back(ev);
+    }
+    SEGCHK(hipEventRecord(w.ev[0], s));
+    return w.ev.data();
+}
+
+// step 4 on (pts, ids) into the segmenter's result buffers
+void group_points(gdf_segmenter* g, const float4* pts, const uint32_t* ids, uint32_t n_cap,
+                  const uint32_t* n_dev, uint32_t nobj, const uint8_t* keep, hipStream_t s,
+                  hipEvent_t* ev) {
+    gdf_segmenter::ObjectPoints& w = g->op;
+    const size_t nb = std::max(n_cap, 1u);
+    const size_t hw = gdf::op_hist_words(n_cap ? n_cap : 1u);
+    SEGCHK(w.pairs0.ensure(nb * 8));
+    SEGCHK(w.pairs1.ensure(nb * 8));
+    SEGCHK(w.hist.ensure(hw * 4));
+    SEGCHK(w.sums.ensure(gdf::op_scan_words(hw) * 4));
+    SEGCHK(w.words.ensure(256));
+    SEGCHK(w.out.ensure(nb * 16));
+    SEGCHK(w.index.ensure(nb * 4));
+    SEGCHK(w.obj_start.ensure(((size_t)nobj + 1) * 4));
+    w.nobj = nobj;
+    w.n_cap = n_cap;
+    w.stream = s;
+    w.n_on_device = n_cap != 0 && n_dev != nullptr;
+    if (n_cap == 0) {  // empty results, nothing to launch
+        SEGCHK(hipMemsetAsync(w.words.p, 0, 8, s));
+        SEGCHK(hipMemsetAsync(w.obj_start.p, 0, ((size_t)nobj + 1) * 4, s));
+        w.nev = 0;
+        w.valid = true;
+        return;
+    }
+    if (n_dev)
+        SEGCHK(hipMemcpyAsync(w.words.as<uint32_t>() + 1, n_dev, 4, hipMemcpyDeviceToDevice, s));
+    gdf::ObjGroupArgs a{};
+    a.pts = pts;
+    a.ids = ids;
+    a.n_dev = n_dev;
+    a.n_cap = n_cap;
+    a.nobj = nobj;
+    a.keep = keep;
+    a.pairs[0] = w.pairs0.as<uint2>();
+    a.pairs[1] = w.pairs1.as<uint2>();
+    a.hist = w.hist.as<uint32_t>();
+    a.sums = w.sums.as<uint32_t>();
+    a.total = w.words.as<uint32_t>();
+    a.out = w.out.as<float4>();
+    a.index = w.index.as<uint32_t>();
+    a.obj_start = w.obj_start.as<uint32_t>();
+    SEGCHK(gdf::launch_object_group(a, s, ev ? ev + 1 : nullptr));
+    if (ev) w.nev = 2 * gdf::op_passes(nobj) + 4;
+    w.valid = true;
+}
+
+void check_nobj(uint32_t nobj) {
+    if (nobj == 0) seg_fail(GDF_ERR_ARG, "object points: no objects");
+    if (nobj > gdf::kOpMaxObjects) seg_fail(GDF_ERR_ARG, "object points: more than 2^24 objects");
+}
+
+gdf::ObjIdArgs id_args(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap,
+                       const uint32_t* n_dev, uint32_t* ids) {
+    gdf::ObjIdArgs a{};
+    a.cells = cells;
+    a.n_dev = n_dev;
+    a.n_cap = n_cap;
+    a.labels = g->labels.as<const uint16_t>();
+    a.lstart = g->lstart.as<const uint32_t>();
+    a.merged = g->mout.as<const uint32_t>();
+    a.T = g->total;
+    a.WH = g->W * g->H;
+    a.L = g->L;
+    a.ncells = (uint64_t)g->W * g->H * g->L;
+    a.ids = ids;
+    return a;
+}
+
+// {total, n} of the last call (waits)
+void op_counts(gdf_segmenter* g, uint32_t* total, uint32_t* n) {
+    gdf_segmenter::ObjectPoints& w = g->op;
+    if (!w.valid) seg_fail(GDF_ERR_STATE, "no object points (call gdf_seg_object_points)");
+    uint32_t h[2] = {0, 0};
+    SEGCHK(hipMemcpyAsync(h, w.words.p, 8, hipMemcpyDeviceToHost, w.stream));
+    SEGCHK(hipStreamSynchronize(w.stream));
+    *total = std::min(h[0], w.n_cap);
+    *n = w.n_on_device ? std::min(h[1], w.n_cap) : w.n_cap;
 }
 
 }  // namespace
@@ -1420,6 +1585,165 @@ int gdf_seg_get_device_results(gdf_segmenter* g, const uint16_t** labels, const 
     if (cent) *cent = g->cent.as<const double>();
     if (conn) *conn = g->conn.as<const uint8_t>();
     return GDF_OK;
+}
+
+// ---- object id per point, points grouped by object -------------------------------
+int gdf_seg_point_object_ids(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap,
+                             const uint32_t* n_dev, uint32_t* ids) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        if (!cells || !ids) seg_fail(GDF_ERR_ARG, "object ids: null argument");
+        need_connections(g);
+        SEGCHK(hipSetDevice(g->device));
+        StreamUse use(g, g->s());
+        ensure_merged(g, g->s());
+        SEGCHK(gdf::launch_object_ids(id_args(g, cells, n_cap, n_dev, ids), g->s()));
+    });
+}
+
+int gdf_seg_group_points(gdf_segmenter* g, const float* pts, const uint32_t* ids, uint32_t n_cap,
+                         const uint32_t* n_dev, uint32_t nobj, const uint8_t* keep) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        if (!pts || !ids) seg_fail(GDF_ERR_ARG, "group points: null argument");
+        check_nobj(nobj);
+        SEGCHK(hipSetDevice(g->device));
+        g->op.valid = false;
+        g->op.have_ids = false;
+        StreamUse use(g, g->s());
+        hipEvent_t* ev = op_events(g, nobj, g->s());
+        group_points(g, reinterpret_cast<const float4*>(pts), ids, n_cap, n_dev, nobj, keep, g->s(), ev);
+    });
+}
+
+int gdf_seg_object_points(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) {
+    if (!g || !e) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        // every refusal comes before the first launch
+        need_connections(g);
+        gdf::FramePoints fp{};
+        const int rc = gdf::engine_frame_points(e, &fp);
+        if (rc != GDF_OK) seg_fail(rc, gdf_last_error());
+        if (fp.gs[0] != g->W || fp.gs[1] != g->H || fp.gs[2] != g->L)
+            seg_fail(GDF_ERR_STATE, "object points: the labelled grid is not the engine's grid");
+        if (fp.device != g->device)
+            seg_fail(GDF_ERR_STATE, "object points: the engine is on another device");
+        SEGCHK(hipSetDevice(g->device));
+        // the labelling, or an earlier gdf_seg_group_points, may have run on the segmenter's stream
+        const hipStream_t s = fp.stream;
+        StreamUse use(g, s);
+        ensure_merged(g, s);  // (the one wait: nobj sizes the object tables)
+        const uint32_t nobj = g->nobj;
+        check_nobj(nobj);
+        gdf_segmenter::ObjectPoints& w = g->op;
+        w.valid = false;
+        w.have_ids = false;
+        SEGCHK(w.ids.ensure((size_t)std::max(fp.cap, 1u) * 4));
+        SEGCHK(w.voxels.ensure((size_t)nobj * 4));
+        SEGCHK(w.keep.ensure(nobj));
+        hipEvent_t* ev = op_events(g, nobj, s);
+        SEGCHK(gdf::launch_object_ids(id_args(g, fp.coords, fp.cap, fp.n_dev, w.ids.as<uint32_t>()), s));
+        SEGCHK(hipMemsetAsync(w.voxels.p, 0, (size_t)nobj * 4, s));
+        gdf::ObjSizeArgs z{};
+        z.stats5 = g->stats5.as<const int32_t>();
+        z.merged = g->mout.as<const uint32_t>();
+        z.lstart = g->lstart.as<const uint32_t>();
+        z.L = g->L;
+        z.T = g->total;
+        z.nobj = nobj;
+        z.min_voxels = min_voxels;
+        z.voxels = w.voxels.as<uint32_t>();
+        z.keep = w.keep.as<uint8_t>();
+        SEGCHK(gdf::launch_object_sizes(z, s));
+        group_points(g, fp.pts, w.ids.as<const uint32_t>(), fp.cap, fp.n_dev, nobj,
+                     w.keep.as<const uint8_t>(), s, ev);
+        w.have_ids = true;
+    });
+}
+
+int gdf_seg_get_object_points(gdf_segmenter* g, uint32_t* nobj, uint32_t* total) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        uint32_t t, n;
+        op_counts(g, &t, &n);
+        if (nobj) *nobj = g->op.nobj;
+        if (total) *total = t;
+    });
+}
+
+int gdf_seg_get_object_points_input(gdf_segmenter* g, uint32_t* n) {
+    if (!g || !n) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        uint32_t t;
+        op_counts(g, &t, n);
+    });
+}
+
+int gdf_seg_download_object_points(gdf_segmenter* g, uint32_t* ids, uint32_t ids_cap, float* pts,
+                                   uint32_t* index, uint32_t pts_cap, uint32_t* obj_start,
+                                   uint32_t* voxels, uint32_t obj_cap) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        gdf_segmenter::ObjectPoints& w = g->op;
+        uint32_t t, n;
+        op_counts(g, &t, &n);
+        if ((ids || voxels) && !w.have_ids)
+            seg_fail(GDF_ERR_STATE, "object points: gdf_seg_group_points computes no ids and no voxels");
+        if (ids && ids_cap < n) seg_fail(GDF_ERR_CAPACITY, "ids capacity too small");
+        if ((pts || index) && pts_cap < t) seg_fail(GDF_ERR_CAPACITY, "points capacity too small");
+        if (obj_start && obj_cap < w.nobj + 1) seg_fail(GDF_ERR_CAPACITY, "obj_start capacity too small");
+        if (voxels && obj_cap < w.nobj) seg_fail(GDF_ERR_CAPACITY, "voxels capacity too small");
+        const hipStream_t s = w.stream;
+        if (ids && n) SEGCHK(hipMemcpyAsync(ids, w.ids.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (pts && t) SEGCHK(hipMemcpyAsync(pts, w.out.p, (size_t)t * 16, hipMemcpyDeviceToHost, s));
+        if (index && t) SEGCHK(hipMemcpyAsync(index, w.index.p, (size_t)t * 4, hipMemcpyDeviceToHost, s));
+        if (obj_start)
+            SEGCHK(hipMemcpyAsync(obj_start, w.obj_start.p, ((size_t)w.nobj + 1) * 4, hipMemcpyDeviceToHost, s));
+        if (voxels) SEGCHK(hipMemcpyAsync(voxels, w.voxels.p, (size_t)w.nobj * 4, hipMemcpyDeviceToHost, s));
+        SEGCHK(hipStreamSynchronize(s));
+    });
+}
+
+int gdf_seg_get_device_object_points(gdf_segmenter* g, const uint32_t** ids, const float** pts,
+                                     const uint32_t** index, const uint32_t** obj_start,
+                                     const uint32_t** voxels, const uint32_t** count) {
+    if (!g) return GDF_ERR_ARG;
+    const gdf_segmenter::ObjectPoints& w = g->op;
+    if (!w.valid) {
+        gdf::set_last_error("no object points (call gdf_seg_object_points)");
+        return GDF_ERR_STATE;
+    }
+    if (ids) *ids = w.have_ids ? w.ids.as<const uint32_t>() : nullptr;
+    if (pts) *pts = w.out.as<const float>();
+    if (index) *index = w.index.as<const uint32_t>();
+    if (obj_start) *obj_start = w.obj_start.as<const uint32_t>();
+    if (voxels) *voxels = w.have_ids ? w.voxels.as<const uint32_t>() : nullptr;
+    if (count) *count = w.words.as<const uint32_t>();
+    return GDF_OK;
+}
+
+int gdf_seg_set_profiling(gdf_segmenter* g, int enable) {
+    if (!g) return GDF_ERR_ARG;
+    g->op.profiling = enable != 0;
+    return GDF_OK;
+}
+
+int gdf_seg_get_object_points_times(gdf_segmenter* g, float* ms, uint32_t cap, uint32_t* count) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        gdf_segmenter::ObjectPoints& w = g->op;
+        if (!w.valid || w.nev < 2) seg_fail(GDF_ERR_STATE, "no profiled object-points call");
+        const uint32_t n = w.nev - 1;
+        if (count) *count = n;
+        if (!ms) return;
+        if (cap < n) seg_fail(GDF_ERR_CAPACITY, "times capacity too small");
+        SEGCHK(hipEventSynchronize(w.ev[w.nev - 1]));
+        for (uint32_t k = 0; k < n; ++k) SEGCHK(hipEventElapsedTime(&ms[k], w.ev[k], w.ev[k + 1]));
+    });
 }
 
 }  // extern "C"

@@ -171,6 +171,12 @@ EXPORTED = [
     "gdf_seg_download_num_labels", "gdf_seg_download_stats", "gdf_seg_download_connections",
     "gdf_seg_download_contours", "gdf_seg_merge_labels", "gdf_seg_get_device_results",
     "gdf_seg_create_objects",
+    # ... object id per point and the points grouped by object
+    "gdf_seg_point_object_ids", "gdf_seg_group_points", "gdf_seg_object_points",
+    "gdf_seg_get_object_points", "gdf_seg_get_object_points_input",
+    "gdf_seg_download_object_points",
+    "gdf_seg_get_device_object_points", "gdf_seg_set_profiling",
+    "gdf_seg_get_object_points_times",
     # include/gdf_filter.h: the radius outlier filter
     "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
     "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
@@ -309,6 +315,15 @@ def load_library(path: str = LIB_PATH):
         "gdf_seg_merge_labels": (i32, [vp, vp, u32, P(u32)]),
         "gdf_seg_get_device_results": (i32, [vp, P(vp), P(vp), P(vp), P(vp)]),
         "gdf_seg_create_objects": (i32, [vp, vp, vp, vp, u32, vp, u32, P(u32)]),
+        "gdf_seg_point_object_ids": (i32, [vp, vp, u32, vp, vp]),
+        "gdf_seg_group_points": (i32, [vp, vp, vp, u32, vp, u32, vp]),
+        "gdf_seg_object_points": (i32, [vp, vp, u32]),
+        "gdf_seg_get_object_points": (i32, [vp, P(u32), P(u32)]),
+        "gdf_seg_get_object_points_input": (i32, [vp, P(u32)]),
+        "gdf_seg_download_object_points": (i32, [vp, vp, u32, vp, vp, u32, vp, vp, u32]),
+        "gdf_seg_get_device_object_points": (i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]),
+        "gdf_seg_set_profiling": (i32, [vp, i32]),
+        "gdf_seg_get_object_points_times": (i32, [vp, vp, u32, P(u32)]),
         "gdf_radius_filter_plan": (i32, [P(RadiusFilterParams), vp, vp]),
         "gdf_radius_filter_points": (i32, [vp, vp, u32, P(RadiusFilterParams), vp, vp, vp]),
         "gdf_radius_filter": (i32, [vp, i32, P(RadiusFilterParams)]),
@@ -1078,6 +1093,7 @@ class GPUDepthmapFusion:
 
 # segmentation flags (include/gdf_segment.h)
 SEG_CONTOURS, SEG_CONNECTIONS, SEG_ALL = 1, 2, 3
+OBJ_NONE = 0xFFFFFFFF  # GDF_OBJ_NONE
 
 
 class Segmenter:
@@ -1178,3 +1194,68 @@ class Segmenter:
         self._check(self._lib.gdf_seg_create_objects(self._h, _ptr(lo), _ptr(cs), objs, n.value,
                                                      _ptr(comps), T, C.byref(n)))
         return cc_objects_as_dict(objs[:n.value]), comps
+
+    def point_object_ids(self, cells_ptr: int, n_cap: int, ids_out_ptr: int, count_ptr: int = 0):
+        """The object id of every cell index (device u32 arrays; count_ptr: a device word holding
+        n, 0: n_cap) into ids_out; needs a labelling with SEG_CONNECTIONS."""
+        self._check(self._lib.gdf_seg_point_object_ids(
+            self._h, C.c_void_p(cells_ptr), n_cap, C.c_void_p(count_ptr or None),
+            C.c_void_p(ids_out_ptr)))
+
+    def group_points(self, points_ptr: int, ids_ptr: int, n_cap: int, nobj: int,
+                     keep_ptr: int = 0, count_ptr: int = 0):
+        """The stable partition of device float4 points by their u32 ids (keep_ptr: u8[nobj] or 0
+        for all; ids >= nobj are dropped); read the result with object_points_results()."""
+        self._check(self._lib.gdf_seg_group_points(
+            self._h, C.c_void_p(points_ptr), C.c_void_p(ids_ptr), n_cap,
+            C.c_void_p(count_ptr or None), nobj, C.c_void_p(keep_ptr or None)))
+
+    def object_points(self, engine: "GPUDepthmapFusion", min_voxels: int = 0):
+        """Ids, object sizes and the per-object clouds of the engine's compacted points, on the
+        engine's stream (after label_engine_grid with SEG_CONNECTIONS)."""
+        self._check(self._lib.gdf_seg_object_points(self._h, engine._h, min_voxels))
+
+    def object_points_counts(self):
+        """(nobj, total) of the last group_points / object_points call (waits)."""
+        nobj, total = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.gdf_seg_get_object_points(self._h, C.byref(nobj), C.byref(total)))
+        return nobj.value, total.value
+
+    def object_points_results(self) -> dict:
+        """points [total, 4], index [total], obj_start [nobj + 1], nobj, total and - after
+        object_points - ids [the point count of that call's frame] and voxels [nobj]."""
+        nobj, total = self.object_points_counts()
+        r = {"nobj": nobj, "total": total,
+             "points": np.zeros((total, 4), np.float32), "index": np.zeros(total, np.uint32),
+             "obj_start": np.zeros(nobj + 1, np.uint32)}
+        self._check(self._lib.gdf_seg_download_object_points(
+            self._h, None, 0, _ptr(r["points"]), _ptr(r["index"]), total, _ptr(r["obj_start"]),
+            None, nobj + 1))
+        if self.object_points_device()["ids"]:
+            n = C.c_uint32(0)
+            self._check(self._lib.gdf_seg_get_object_points_input(self._h, C.byref(n)))
+            n_ids = n.value
+            r["ids"] = np.zeros(n_ids, np.uint32)
+            r["voxels"] = np.zeros(nobj, np.uint32)
+            self._check(self._lib.gdf_seg_download_object_points(
+                self._h, _ptr(r["ids"]), n_ids, None, None, 0, None, _ptr(r["voxels"]), nobj))
+        return r
+
+    def object_points_device(self) -> dict:
+        """Device pointers (ints; ids and voxels 0 after group_points) of the last result."""
+        p = [C.c_void_p() for _ in range(6)]
+        self._check(self._lib.gdf_seg_get_device_object_points(self._h, *[C.byref(x) for x in p]))
+        keys = ("ids", "points", "index", "obj_start", "voxels", "count")
+        return {k: (x.value or 0) for k, x in zip(keys, p)}
+
+    def set_profiling(self, enable: bool):
+        self._check(self._lib.gdf_seg_set_profiling(self._h, int(bool(enable))))
+
+    def object_points_times(self) -> np.ndarray:
+        """Milliseconds of the last profiled call: [ids + sizes], per pass [count + scan, scatter],
+        [gather], [starts]."""
+        n = C.c_uint32(0)
+        self._check(self._lib.gdf_seg_get_object_points_times(self._h, None, 0, C.byref(n)))
+        ms = np.zeros(n.value, np.float32)
+        self._check(self._lib.gdf_seg_get_object_points_times(self._h, _ptr(ms), n.value, C.byref(n)))
+        return ms
