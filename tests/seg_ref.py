@@ -70,8 +70,36 @@ def stats(lab: np.ndarray, n: int):
     return st, ce
 
 
-def external_contours(img: np.ndarray):
-    """findContours(img, RETR_EXTERNAL, CHAIN_APPROX_NONE): list of (k, 2) int arrays."""
+SCAN_STEP = 256  # padded columns the GPU scan reads per step (k_cc_contours); census only
+
+
+def _count(census, kind, r=None):
+    if census is None:
+        return
+    if r is None:
+        census[kind] = census.get(kind, 0) + 1
+    else:
+        d = census.setdefault(kind, {})
+        d[r] = d.get(r, 0) + 1
+
+
+def external_contours(img: np.ndarray, census: dict | None = None):
+    """findContours(img, RETR_EXTERNAL, CHAIN_APPROX_NONE): list of (k, 2) int arrays.
+
+    census (optional, results unchanged): counts of the raster scan's events by kind, in terms of
+    the SCAN_STEP-column steps in which the GPU scan reads a row (X = the padded column of a
+    0 -> 1 transition, `step` = SCAN_STEP * (X // SCAN_STEP)):
+      taken / skipped                 the start is traced / lies inside a hole;
+      skipped_lnbd_earlier_step       skipped with lnbd < step (the cached value decides);
+      taken_lnbd_earlier_step         taken with lnbd != 0, lnbd < step (its value <= 0);
+      start_at_step_edge[r]           a taken start with X % SCAN_STEP == r in (255, 0, 1), X > 2;
+      second_start_stale_lnbd         taken with lnbd != 0, lnbd < step, after another start of
+                                      the row was traced since lnbd last changed;
+      skipped_lnbd_run_start_earlier_step   skipped with lnbd < step where lnbd was last set at
+                                      the BEGINNING of a marked run (a wall two or more pixels
+                                      thick whose far side is unmarked: the value cached there is
+                                      the only one that decides).
+    """
     H, W = img.shape
     Hp, Wp = H + 2, W + 2
     a = [[0] * Wp for _ in range(Hp)]
@@ -116,22 +144,40 @@ def external_contours(img: np.ndarray):
     found = []
     for y in range(1, Hp - 1):
         prev, lnbd, x = 0, 0, 1
+        traced_at = None  # census: the lnbd under which the row's last start was traced
+        at_run_start = False  # census: lnbd was last set where a marked run begins
         while x < Wp - 1:
             p = a[y][x]
             if p == prev:
                 x += 1
                 continue
             if prev == 0 and p == 1:
+                earlier = lnbd < SCAN_STEP * (x // SCAN_STEP)
                 if a[y][lnbd] <= 0:
+                    _count(census, "taken")
+                    if lnbd != 0 and earlier:
+                        _count(census, "taken_lnbd_earlier_step")
+                        if traced_at == lnbd:
+                            _count(census, "second_start_stale_lnbd")
+                    if x > 2 and x % SCAN_STEP in (SCAN_STEP - 1, 0, 1):
+                        _count(census, "start_at_step_edge", x % SCAN_STEP)
+                    traced_at = lnbd
                     found.append(np.array(fetch(x, y), np.int32).reshape(-1, 2))
                     prev = a[y][x]
                     x += 1
                     continue
+                _count(census, "skipped")
+                if earlier:
+                    _count(census, "skipped_lnbd_earlier_step")
+                    if at_run_start:
+                        _count(census, "skipped_lnbd_run_start_earlier_step")
             elif p == 0 and prev >= 1 and (prev & -2):
                 lnbd = x - 1
+                at_run_start = False
             prev = p
             if prev & -2:
                 lnbd = x
+                at_run_start = True
             x += 1
     return found[::-1]
 

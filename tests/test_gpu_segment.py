@@ -2,7 +2,9 @@
 (oracle/seg_oracle.c): labels, num_labels, stats, centroids, labelsToContours, contours, layer
 connections, merged labels — on random blob grids (odd sizes, tile-crossing components), the
 launch-default 400 x 400 x 21 grid, a layer too large for LDS (global-scratch contour path),
-empty / full layers, and the engine's own occupancy grid after dense frames."""
+empty / full layers, and the engine's own occupancy grid after dense frames.  Random blobs find
+the common paths; the shapes built for the kernels' edges (tile corners, scan steps, the LDS limit,
+more than 256 layers, the label limit, flags, unaligned grids) are in test_gpu_segment_shapes.py."""
 import numpy as np
 import pytest
 
