@@ -2156,32 +2156,51 @@ void partition_runs(gdf_engine* e, uint32_t nparts, float* send_pts, uint32_t* s
 }
 
 // ---- radius outlier filter (include/gdf_filter.h, gdf_filter.hip) -------------------------------
-// n = n_dev ? min(*n_dev, n_cap) : n_cap points of `in`; keep == nullptr: the slot's own flags
-void radius_filter_run(gdf_engine* e, const float4* in, const uint32_t* n_dev, uint32_t n_cap,
-                       const gdf_radius_filter_params* p, float4* out, uint32_t* out_count,
-                       uint8_t* keep) {
+RadiusPlan radius_plan_or_fail(RadiusTable table, const gdf_radius_filter_params* p) {
     RadiusPlan pl;
-    if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
-    if (n_cap > (1u << 31)) fail(GDF_ERR_ARG, "radius filter: more than 2^31 points");
+    if (radius_plan(table, p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    return pl;
+}
+
+// One filter call over the cell table of `table` and its plan pl.  Dense: n = n_dev ? min(*n_dev,
+// n_cap) : n_cap points of `in` (seg_start, nseg and out_start unused).  Sparse: segments from
+// seg_start (device, nseg + 1), or - seg_start == nullptr - the one segment [0, min(*n_dev, n_cap)).
+// keep == nullptr: the slot's own flags.
+void radius_run(gdf_engine* e, RadiusTable table, const RadiusPlan& pl, const float4* in, uint32_t n_cap,
+                const uint32_t* seg_start, const uint32_t* n_dev, uint32_t nseg,
+                const gdf_radius_filter_params* p, float4* out, uint32_t* out_start, uint32_t* out_count,
+                uint8_t* keep) {
+    const bool sparse = table == RadiusTable::Sparse;
+    if (sparse) {
+        if (nseg < 1 || nseg > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: 1..64 segments");
+        if (n_cap > kRfMaxSegPoints) fail(GDF_ERR_ARG, "radius filter: more than 2^30 points");
+    } else if (n_cap > (1u << 31)) {
+        fail(GDF_ERR_ARG, "radius filter: more than 2^31 points");
+    }
     Slot::Filter& w = e->sl().rf;
     hipStream_t st = e->s();
     const size_t nb = std::max<uint32_t>(n_cap, 1u);
     const uint32_t nt = std::max<uint32_t>(rf_tiles(n_cap), 1u);
+    const uint32_t M = sparse ? rf_table_slots(n_cap) : pl.ncells;  // the table's length
     w.cell.ensure(nb * 4);
     w.rank.ensure(nb * 4);
     w.sorted.ensure(nb * 16);
     w.scell.ensure(nb * 4);
     if (!keep) w.keep.ensure(nb);
-    w.start.ensure(((size_t)pl.ncells + 1) * 4);
-    w.cell_sums.ensure(rf_scan_words(pl.ncells) * 4);
+    w.start.ensure(((size_t)M + 1) * 4);
+    w.cell_sums.ensure(rf_scan_words(M) * 4);
     w.tile_cnt.ensure(((size_t)nt + 1) * 4);
     w.tile_off.ensure(((size_t)nt + 1) * 4);
     w.tile_sums.ensure(rf_scan_words(nt) * 4);
-    // the cell counters are zero between calls (the scan that reads them last clears them); a
-    // grown buffer, or one a failed call may have left set, is cleared whole
-    if (!w.cnt.ensure_zero(((size_t)pl.ncells + 1) * 4, st) && w.cnt_dirty)
+    // counters zero and (Sparse) keys empty between calls: the scan that reads the counters last
+    // clears them, the compaction empties the slots it filled; a grown buffer, or one a failed call
+    // may have left set, is cleared whole
+    if (!w.cnt.ensure_zero(((size_t)M + 1) * 4, st) && w.cnt_dirty)
         HIPCHK(hipMemsetAsync(w.cnt.p, 0, w.cnt.bytes, st));
+    if (sparse && (w.keys.ensure((size_t)M * 8) || w.keys_dirty))
+        HIPCHK(hipMemsetAsync(w.keys.p, 0xFF, w.keys.bytes, st));
     RadiusArgs a{};
+    a.table = table;
     a.in = in;
     a.n_dev = n_dev;
     a.n_cap = n_cap;
@@ -2191,7 +2210,6 @@ void radius_filter_run(gdf_engine* e, const float4* in, const uint32_t* n_dev, u
         a.inv[k] = pl.inv[k];
         a.cells[k] = pl.cells[k];
     }
-    a.ncells = pl.ncells;
     a.r2 = pl.r2;
     a.min_neighbors = p->min_neighbors;
     a.cell = w.cell.as<uint32_t>();
@@ -2207,119 +2225,34 @@ void radius_filter_run(gdf_engine* e, const float4* in, const uint32_t* n_dev, u
     a.tile_sums = w.tile_sums.as<uint32_t>();
     a.out = out;
     a.out_count = out_count;
+    if (sparse) {
+        a.nslots = M;
+        a.keys = w.keys.as<uint64_t>();
+        a.seg_start = seg_start;
+        a.nseg = nseg;
+        a.out_start = out_start;
+        w.keys_dirty = true;
+    } else {
+        a.ncells = M;
+    }
     w.cnt_dirty = true;
     HIPCHK(launch_radius_filter(a, st));
     w.cnt_dirty = false;
+    if (sparse) w.keys_dirty = false;
 }
 
-// the stage call: the addressed slot's points or voxelized points, count on the device
-void radius_filter_stage(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
+// The stage call: the addressed slot's points or voxelized points, counts on the device.  Dense: one
+// frame's cloud.  Sparse: a frame or a batch, one segment per frame, the ranges read on the device.
+void radius_stage(gdf_engine* e, RadiusTable table, int source, const gdf_radius_filter_params* p) {
     Slot& q = e->sl();
+    const bool sparse = table == RadiusTable::Sparse;
     if (source != GDF_RF_POINTS && source != GDF_RF_VOXELIZED) fail(GDF_ERR_ARG, "radius filter: bad source");
-    if (q.nframes > 1 && q.frame_pts) fail(GDF_ERR_STATE, "radius filter: not for a multi-frame batch");
+    if (!sparse && q.nframes > 1 && q.frame_pts) fail(GDF_ERR_STATE, "radius filter: not for a multi-frame batch");
     if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "radius filter before the frame's compaction");
     if (q.frame_parts)
         fail(GDF_ERR_STATE, "radius filter: not for a frame armed with the emit partition");
-    const float4* in;
-    const uint32_t* n_dev;
-    uint32_t cap;
-    if (source == GDF_RF_VOXELIZED) {
-        if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "radius filter before the frame's voxelize");
-        in = q.d_vox.as<float4>();
-        n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
-        cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, 1u << 31);
-    } else {
-        in = q.d_pts.as<float4>();
-        n_dev = q.d_misc.as<uint32_t>() + kCount;
-        cap = q.n_total;
-    }
-    RadiusPlan pl;
-    if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
-    q.rf.valid = false;
-    q.rf.out.ensure((size_t)std::max<uint32_t>(cap, 1u) * 16);
-    q.rf.count.ensure(256);
-    q.rf.cap = cap;
-    q.rf.nseg = 0;  // (one cloud: no ranges of a batch)
-    radius_filter_run(e, in, n_dev, cap, p, q.rf.out.as<float4>(), q.rf.count.as<uint32_t>(), nullptr);
-    q.rf.valid = true;
-}
-
-// The segmented filter over the sparse cell table: segments from seg_start (device, nseg + 1), or -
-// seg_start == nullptr - the one segment [0, min(*n_dev, n_cap)).  keep == nullptr: the slot's own
-// flags.
-void radius_segments_run(gdf_engine* e, const float4* in, uint32_t n_cap, const uint32_t* seg_start,
-                         const uint32_t* n_dev, uint32_t nseg, const gdf_radius_filter_params* p,
-                         float4* out, uint32_t* out_start, uint32_t* out_count, uint8_t* keep) {
-    RadiusPlan pl;
-    if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
-    if (nseg < 1 || nseg > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: 1..64 segments");
-    if (n_cap > kRfMaxSegPoints) fail(GDF_ERR_ARG, "radius filter: more than 2^30 points");
-    Slot::Filter& w = e->sl().rf;
-    hipStream_t st = e->s();
-    const size_t nb = std::max<uint32_t>(n_cap, 1u);
-    const uint32_t nt = std::max<uint32_t>(rf_tiles(n_cap), 1u);
-    const uint32_t H = rf_table_slots(n_cap);
-    w.cell.ensure(nb * 4);
-    w.rank.ensure(nb * 4);
-    w.sorted.ensure(nb * 16);
-    w.scell.ensure(nb * 4);
-    if (!keep) w.keep.ensure(nb);
-    w.start.ensure(((size_t)H + 1) * 4);
-    w.cell_sums.ensure(rf_scan_words(H) * 4);
-    w.tile_cnt.ensure(((size_t)nt + 1) * 4);
-    w.tile_off.ensure(((size_t)nt + 1) * 4);
-    w.tile_sums.ensure(rf_scan_words(nt) * 4);
-    // counters zero and keys empty between calls (the scan zeroes the counters, the compaction
-    // empties the slots it filled); a grown buffer, or one a failed call may have left set, is
-    // cleared whole
-    if (!w.cnt.ensure_zero(((size_t)H + 1) * 4, st) && w.cnt_dirty)
-        HIPCHK(hipMemsetAsync(w.cnt.p, 0, w.cnt.bytes, st));
-    if (w.keys.ensure((size_t)H * 8) || w.keys_dirty)
-        HIPCHK(hipMemsetAsync(w.keys.p, 0xFF, w.keys.bytes, st));
-    RadiusSegArgs a{};
-    a.in = in;
-    a.n_cap = n_cap;
-    a.seg_start = seg_start;
-    a.n_dev = n_dev;
-    a.nseg = nseg;
-    for (int k = 0; k < 3; ++k) {
-        a.lo[k] = p->lower[k];
-        a.hi[k] = p->upper[k];
-        a.inv[k] = pl.inv[k];
-        a.cells[k] = pl.cells[k];
-    }
-    a.r2 = pl.r2;
-    a.min_neighbors = p->min_neighbors;
-    a.nslots = H;
-    a.keys = w.keys.as<uint64_t>();
-    a.cnt = w.cnt.as<uint32_t>();
-    a.start = w.start.as<uint32_t>();
-    a.cell_sums = w.cell_sums.as<uint32_t>();
-    a.slot = w.cell.as<uint32_t>();
-    a.rank = w.rank.as<uint32_t>();
-    a.sorted = w.sorted.as<float4>();
-    a.sslot = w.scell.as<uint32_t>();
-    a.keep = keep ? keep : w.keep.as<uint8_t>();
-    a.tile_cnt = w.tile_cnt.as<uint32_t>();
-    a.tile_off = w.tile_off.as<uint32_t>();
-    a.tile_sums = w.tile_sums.as<uint32_t>();
-    a.out = out;
-    a.out_start = out_start;
-    a.out_count = out_count;
-    w.cnt_dirty = w.keys_dirty = true;
-    HIPCHK(launch_radius_filter_segments(a, st));
-    w.cnt_dirty = w.keys_dirty = false;
-}
-
-// the stage call for a frame or a batch: one segment per frame, the ranges read on the device
-void radius_filter_batch_stage(gdf_engine* e, int source, const gdf_radius_filter_params* p) {
-    Slot& q = e->sl();
-    if (source != GDF_RF_POINTS && source != GDF_RF_VOXELIZED) fail(GDF_ERR_ARG, "radius filter: bad source");
-    if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "radius filter before the frame's compaction");
-    if (q.frame_parts)
-        fail(GDF_ERR_STATE, "radius filter: not for a frame armed with the emit partition");
-    const bool batch = q.nframes > 1;
-    if (q.nframes > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: more than 64 frames");
+    const bool batch = sparse && q.nframes > 1;
+    if (sparse && q.nframes > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: more than 64 frames");
     const float4* in;
     const uint32_t *n_dev, *seg_start;
     uint32_t cap;
@@ -2328,7 +2261,7 @@ void radius_filter_batch_stage(gdf_engine* e, int source, const gdf_radius_filte
         in = q.d_vox.as<float4>();
         n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
         seg_start = q.d_fvox.as<uint32_t>();
-        cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, kRfMaxSegPoints);
+        cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, sparse ? kRfMaxSegPoints : 1u << 31);
     } else {
         in = q.d_pts.as<float4>();
         n_dev = q.d_misc.as<uint32_t>() + kCount;
@@ -2336,17 +2269,16 @@ void radius_filter_batch_stage(gdf_engine* e, int source, const gdf_radius_filte
         cap = q.n_total;
     }
     if (batch && !seg_start) fail(GDF_ERR_STATE, "radius filter: the batch has no frame ranges");
-    RadiusPlan pl;
-    if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+    const RadiusPlan pl = radius_plan_or_fail(table, p);
     q.rf.valid = false;
     q.rf.out.ensure((size_t)std::max<uint32_t>(cap, 1u) * 16);
     q.rf.count.ensure(256);
-    q.rf.seg_out.ensure((kRfMaxSegs + 1) * 4);
+    if (sparse) q.rf.seg_out.ensure((kRfMaxSegs + 1) * 4);
     q.rf.cap = cap;
-    q.rf.nseg = q.nframes;
-    radius_segments_run(e, in, cap, batch ? seg_start : nullptr, batch ? nullptr : n_dev, q.nframes, p,
-                        q.rf.out.as<float4>(), q.rf.seg_out.as<uint32_t>(), q.rf.count.as<uint32_t>(),
-                        nullptr);
+    q.rf.nseg = sparse ? q.nframes : 0;  // (0: one cloud, no ranges of a batch)
+    radius_run(e, table, pl, in, cap, batch ? seg_start : nullptr, batch ? nullptr : n_dev, q.rf.nseg, p,
+               q.rf.out.as<float4>(), sparse ? q.rf.seg_out.as<uint32_t>() : nullptr,
+               q.rf.count.as<uint32_t>(), nullptr);
     q.rf.valid = true;
 }
 
@@ -3121,11 +3053,11 @@ int gdf_process_frame(gdf_engine* e, const gdf_frame_params* p, gdf_frame_result
             run_frame(e, false);
         }
         if (rf_batch)  // after the batch's chain, outside its captured graph
-            radius_filter_batch_stage(e, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
-                                      &e->rfb_params);
+            radius_stage(e, RadiusTable::Sparse, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
+                         &e->rfb_params);
         else if (e->rf_armed)  // after the frame's chain, outside its captured graph
-            radius_filter_stage(e, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
-                                &e->rf_params);
+            radius_stage(e, RadiusTable::Dense, p->enable_voxel_filter ? GDF_RF_VOXELIZED : GDF_RF_POINTS,
+                         &e->rf_params);
         res.num_depth_points = e->depth_total;
         res.num_points_total = e->sl().n_total;
         if (p->synchronous) {
@@ -3177,8 +3109,9 @@ int gdf_radius_filter_points(gdf_engine* e, const float* in, uint32_t n,
     return guarded(e, [&] {
         if (!p || !out_count || (n && (!in || !out))) fail(GDF_ERR_ARG, "radius filter: null argument");
         if (n && in == out) fail(GDF_ERR_ARG, "radius filter: in-place is not supported");
-        radius_filter_run(e, reinterpret_cast<const float4*>(in), nullptr, n, p,
-                          reinterpret_cast<float4*>(out), out_count, keep);
+        radius_run(e, RadiusTable::Dense, radius_plan_or_fail(RadiusTable::Dense, p),
+                   reinterpret_cast<const float4*>(in), n, nullptr, nullptr, 0, p,
+                   reinterpret_cast<float4*>(out), nullptr, out_count, keep);
     });
 }
 
@@ -3186,7 +3119,7 @@ int gdf_radius_filter(gdf_engine* e, int source, const gdf_radius_filter_params*
     ENGINE_OR_FAIL(e);
     return guarded(e, [&] {
         if (!p) fail(GDF_ERR_ARG, "radius filter: null parameters");
-        radius_filter_stage(e, source, p);
+        radius_stage(e, RadiusTable::Dense, source, p);
     });
 }
 
@@ -3194,8 +3127,7 @@ int gdf_set_radius_filter(gdf_engine* e, int enable, const gdf_radius_filter_par
     ENGINE_OR_FAIL(e);
     return guarded(e, [&] {
         if (enable) {
-            RadiusPlan pl;
-            if (radius_plan(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+            radius_plan_or_fail(RadiusTable::Dense, p);
             e->rf_params = *p;
         }
         e->rf_armed = enable != 0;
@@ -3212,8 +3144,9 @@ int gdf_radius_filter_segments(gdf_engine* e, const float* in, uint32_t n_cap,
             fail(GDF_ERR_ARG, "radius filter: null argument");
         if (nseg < 1 || nseg > kRfMaxSegs) fail(GDF_ERR_ARG, "radius filter: 1..64 segments");
         if (n_cap && in == out) fail(GDF_ERR_ARG, "radius filter: in-place is not supported");
-        radius_segments_run(e, reinterpret_cast<const float4*>(in), n_cap, seg_start, nullptr, nseg, p,
-                            reinterpret_cast<float4*>(out), out_seg_start, out_count, keep);
+        radius_run(e, RadiusTable::Sparse, radius_plan_or_fail(RadiusTable::Sparse, p),
+                   reinterpret_cast<const float4*>(in), n_cap, seg_start, nullptr, nseg, p,
+                   reinterpret_cast<float4*>(out), out_seg_start, out_count, keep);
     });
 }
 
@@ -3221,7 +3154,7 @@ int gdf_radius_filter_batch(gdf_engine* e, int source, const gdf_radius_filter_p
     ENGINE_OR_FAIL(e);
     return guarded(e, [&] {
         if (!p) fail(GDF_ERR_ARG, "radius filter: null parameters");
-        radius_filter_batch_stage(e, source, p);
+        radius_stage(e, RadiusTable::Sparse, source, p);
     });
 }
 
@@ -3229,8 +3162,7 @@ int gdf_set_radius_filter_batch(gdf_engine* e, int enable, const gdf_radius_filt
     ENGINE_OR_FAIL(e);
     return guarded(e, [&] {
         if (enable) {
-            RadiusPlan pl;
-            if (radius_plan_sparse(p, &pl) != GDF_OK) fail(GDF_ERR_ARG, g_last_error);
+            radius_plan_or_fail(RadiusTable::Sparse, p);
             e->rfb_params = *p;
         }
         e->rfb_armed = enable != 0;

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "gdf_object_points.hpp"
+#include "gdf_scan.hpp"
 
 namespace gdf {
 namespace {
@@ -74,108 +75,6 @@ __global__ __launch_bounds__(kT) void k_op_sizes(const ObjSizeArgs a) {
 __global__ __launch_bounds__(kT) void k_op_keep(const ObjSizeArgs a) {
     const uint32_t o = blockIdx.x * kT + threadIdx.x;
     if (o < a.nobj) a.keep[o] = a.voxels[o] >= max(a.min_voxels, 1u) ? 1 : 0;
-}
-
-// ---- exclusive scan of m u32 words in place: buf[i] = sum of buf[< i], buf[m] = the total ------
-// exclusive scan of v over the block's 256 threads; *total = the block's sum.  sh: kWaves words
-__device__ __forceinline__ uint32_t op_block_scan(uint32_t v, uint32_t* total, uint32_t* sh) {
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= (uint32_t)d) incl += t;
-    }
-    if (lane == 63u) sh[w] = incl;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kWaves; ++k) {
-        const uint32_t s = sh[k];
-        if (k < w) base += s;
-        tot += s;
-    }
-    __syncthreads();  // (sh is rewritten by the next scan)
-    *total = tot;
-    return base + incl - v;
-}
-
-// one block, any m (a carry between its chunks of kOpScanTile)
-__global__ __launch_bounds__(kT) void k_op_scan_block(uint32_t* buf, uint32_t m, uint32_t* total_out) {
-    __shared__ uint32_t sh[kWaves];
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < m; base += kOpScanTile) {
-        const uint32_t first = base + threadIdx.x * 4u;
-        uint32_t v[4], s = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            v[k] = first + k < m ? buf[first + k] : 0u;
-            s += v[k];
-        }
-        uint32_t tot;
-        uint32_t o = carry + op_block_scan(s, &tot, sh);  // (its barriers order reads before writes)
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k)
-            if (first + k < m) {
-                buf[first + k] = o;
-                o += v[k];
-            }
-        carry += tot;
-    }
-    if (threadIdx.x == 0) {
-        buf[m] = carry;
-        if (total_out) *total_out = carry;
-    }
-}
-
-__global__ __launch_bounds__(kT) void k_op_scan_sums(const uint32_t* buf, uint32_t m, uint32_t* sums) {
-    __shared__ uint32_t sh[kWaves];
-    const uint32_t first = blockIdx.x * kOpScanTile + threadIdx.x * 4u;
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) s += first + k < m ? buf[first + k] : 0u;
-    uint32_t tot;
-    op_block_scan(s, &tot, sh);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-// sums: the exclusive scan of the tile sums, sums[nt] = the total
-__global__ __launch_bounds__(kT) void k_op_scan_apply(uint32_t* buf, const uint32_t* sums, uint32_t m,
-                                                       uint32_t nt, uint32_t* total_out) {
-    __shared__ uint32_t sh[kWaves];
-    const uint32_t first = blockIdx.x * kOpScanTile + threadIdx.x * 4u;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-        v[k] = first + k < m ? buf[first + k] : 0u;
-        s += v[k];
-    }
-    uint32_t tot;
-    uint32_t o = sums[blockIdx.x] + op_block_scan(s, &tot, sh);
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k)
-        if (first + k < m) {
-            buf[first + k] = o;
-            o += v[k];
-        }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        buf[m] = sums[nt];
-        if (total_out) *total_out = sums[nt];
-    }
-}
-
-constexpr uint32_t kScanOneBlock = 8 * kOpScanTile;  // up to here one block scans alone
-
-hipError_t op_scan(uint32_t* buf, uint32_t m, uint32_t* sums, uint32_t* total_out, hipStream_t st) {
-    if (m <= kScanOneBlock) {
-        hipLaunchKernelGGL(k_op_scan_block, dim3(1), dim3(kT), 0, st, buf, m, total_out);
-        return hipGetLastError();
-    }
-    const uint32_t nt = (m + kOpScanTile - 1) / kOpScanTile;
-    hipLaunchKernelGGL(k_op_scan_sums, dim3(nt), dim3(kT), 0, st, buf, m, sums);
-    hipLaunchKernelGGL(k_op_scan_block, dim3(1), dim3(kT), 0, st, sums, nt, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_op_scan_apply, dim3(nt), dim3(kT), 0, st, buf, sums, m, nt, total_out);
-    return hipGetLastError();
 }
 
 // ---- the partition passes -----------------------------------------------------------------------
@@ -348,7 +247,7 @@ hipError_t launch_object_group(const ObjGroupArgs& a, hipStream_t st, hipEvent_t
         else
             hipLaunchKernelGGL(k_op_hist<false>, dim3(nt), dim3(kT), 0, st, a, src, shift);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = op_scan(a.hist, m, a.sums, a.total, st)) != hipSuccess) return e;
+        if ((e = launch_excl_scan(a.hist, a.hist, m, a.sums, false, a.total, st)) != hipSuccess) return e;
         if (ev && (e = hipEventRecord(ev[k++], st)) != hipSuccess) return e;
         if (p == 0)
             hipLaunchKernelGGL(k_op_scatter<true>, dim3(nt), dim3(kT), 0, st, a, src, dst, shift);

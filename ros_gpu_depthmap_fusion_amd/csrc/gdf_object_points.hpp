@@ -6,11 +6,11 @@
 #include <stdint.h>
 
 #include "gdf.h"
+#include "gdf_scan.hpp"
 
 namespace gdf {
 
 constexpr uint32_t kOpTile = 2048;            // items per partition tile (256 threads x 8 rounds)
-constexpr uint32_t kOpScanTile = 1024;        // words per scan tile (256 threads x 4)
 constexpr uint32_t kOpMaxObjects = 1u << 24;  // nobj cap: three 8-bit passes
 constexpr uint32_t kOpNone = 0xFFFFFFFFu;     // GDF_OBJ_NONE
 constexpr uint32_t kOpLdsLayers = 8192;       // up to here the lstart table goes through LDS
@@ -18,7 +18,7 @@ constexpr uint32_t kOpLdsLayers = 8192;       // up to here the lstart table goe
 inline uint32_t op_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kOpTile - 1) / kOpTile); }
 // words of the digit table of an n_cap-item call (256 digits per tile, digit-major) + the total
 inline size_t op_hist_words(uint32_t n_cap) { return (size_t)256 * op_tiles(n_cap) + 1; }
-inline size_t op_scan_words(size_t m) { return (m + kOpScanTile - 1) / kOpScanTile + 1; }
+inline size_t op_scan_words(size_t m) { return scan_words(m); }
 // 8-bit passes that order ids below nobj: 1 up to 256 objects, 2 up to 65 536, 3 up to 2^24
 inline uint32_t op_passes(uint32_t nobj) { return nobj <= 256u ? 1u : nobj <= 65536u ? 2u : 3u; }
 

@@ -125,6 +125,27 @@ def test_partition_sizes_and_patterns(seg, nobj):
     assert kept_any
 
 
+@pytest.mark.parametrize("n,words", [(32 * TILE, 8192), (32 * TILE + 1, 8448)])
+def test_partition_on_both_sides_of_the_scan_switch(seg, n, words):
+    """The digit table of an n-point call has 256 words per tile.  Up to 8 scan tiles of 1024 words
+    (32 partition tiles) one block scans it alone; from 33 partition tiles on the scan takes three
+    launches (tile sums, their scan, apply).  Two passes (nobj 257) on either side of the switch."""
+    assert 256 * -(-n // TILE) == words and (words <= 8 * 1024) == (n == 32 * TILE)
+    nobj = 257
+    rng = np.random.default_rng(n)
+    pts = odd_points(rng, n)
+    pats = id_patterns(rng, n, nobj)
+    for name in ("random", "keep_mask"):
+        ids, keep = pats[name]
+        want = opr.group(pts, ids, nobj, keep)
+        got = run_group(seg, pts, ids, nobj, keep)
+        try:
+            opr.assert_equal(got, want)
+        except AssertionError as e:
+            raise AssertionError(f"n {n} nobj {nobj} {name}: {e}") from None
+        assert want["total"] > 0
+
+
 @pytest.mark.parametrize("n,count", [(4099, 4099), (4099, 2048), (1025, 63), (65, 0), (64, 200)])
 def test_device_count_and_canary_rows(seg, n, count):
     """A device count below n_cap: the rows behind it are neither read nor written, and nothing

@@ -171,6 +171,24 @@ def test_plan_extremes(gpu, name):
     check_scene(gpu, name)
 
 
+# ---- both paths of the cell counters' scan -------------------------------------------------------
+def test_scenes_sit_on_both_sides_of_the_cell_scan_switch():
+    """The scan of the cell counters runs in one block up to 8192 cells and in three launches above.
+    Scenes of at most 4097 points already take both paths - wave_n4097_h1 (14^3 cells, run by
+    test_wave_and_tile_edges) and extreme_both_caps (2^22 cells, run by test_plan_extremes) - so
+    this test only pins their plans."""
+    from ros_gpu_depthmap_fusion_amd.gdf import radius_filter_plan
+    assert "wave_n4097_h1" in S.WAVE_NAMES and "extreme_both_caps" in S.EXTREME_NAMES
+    ncells = {}
+    for name in ("wave_n4097_h1", "extreme_both_caps"):
+        s = S.get(name)
+        assert len(s["pts"]) <= 4097
+        ncells[name] = int(np.prod(np.asarray(radius_filter_plan(s["lower"], s["upper"], s["radius"])[0],
+                                              np.uint64)))
+    assert ncells == {"wave_n4097_h1": 2744, "extreme_both_caps": 1 << 22}
+    assert ncells["wave_n4097_h1"] <= 8192 < ncells["extreme_both_caps"]
+
+
 # ---- more than one block of every kernel --------------------------------------------------------
 def test_multi_block_paths(gpu):
     name = "multiblock_65537"

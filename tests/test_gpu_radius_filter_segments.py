@@ -172,6 +172,11 @@ def test_one_engine_reused_across_sizes_boxes_and_radii(gpu_engine_factory):
     eng = gpu_engine_factory()
     try:
         assert [len(C.get(n)["pts"]) for n in C.REUSE_NAMES] == [8191, 31, 4097, 514]
+        # the table's slots on both sides of the scan's switch from one block (<= 8192 words) to three
+        # launches.  The expression mirrors rf_table_slots of csrc/gdf_filter.hpp (the library does not
+        # export it): it pins the scenes' sizes, it would not notice a change of that function.
+        slots = [max(1024, 1 << (2 * max(len(C.get(n)["pts"]), 512) - 1).bit_length()) for n in C.REUSE_NAMES]
+        assert slots[3] == 2048 and slots[0] == 16384          # twin, lattice
         for rounds in range(2):                                # (a table left from a larger call)
             for name in C.REUSE_NAMES:
                 assert_mixed(name)
