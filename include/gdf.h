@@ -315,6 +315,10 @@ int gdf_get_graph_stats(gdf_engine* engine, uint64_t* captures, uint64_t* replay
 /* Instrumentation (no reference counterpart): the items the last synchronous gdf_process_frame's
  * voxelize sorted - runs of equal voxel keys (*runs = 1) or points (*runs = 0). */
 int gdf_last_sort_items(gdf_engine* engine, uint32_t* items, int* runs);
+/* Instrumentation (no reference counterpart): the voxel groups that the last voxelize over sorted
+ * runs handed from k_group_runs to k_group_runs_big - *queued below the huge region, *huge in it
+ * (zero after a voxelize over sorted points).  Waits for the engine's stream. */
+int gdf_last_group_queue(gdf_engine* engine, uint32_t* queued, uint32_t* huge);
 
 /* ---- orphan shaders of the reference (device buffers, the engine's stream) ------------------ */
 /* mask_dilate (shader/mask_dilate.glsl:40-67; never dispatched by the reference): for every pixel

@@ -3081,6 +3081,20 @@ int gdf_last_sort_items(gdf_engine* e, uint32_t* items, int* runs) {
     return GDF_OK;
 }
 
+int gdf_last_group_queue(gdf_engine* e, uint32_t* queued, uint32_t* huge) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        uint32_t q[3] = {0u, 0u, 0u};  // (kCtrRunQueue: appends, draws, huge appends)
+        if (e->sl().d_ctrs.p) {
+            HIPCHK(hipStreamSynchronize(e->s()));
+            HIPCHK(hipMemcpy(q, e->sl().d_ctrs.as<unsigned long long>() + kCtrRunQueue, sizeof(q),
+                             hipMemcpyDeviceToHost));
+        }
+        if (queued) *queued = q[0];
+        if (huge) *huge = q[2];
+    });
+}
+
 int gdf_mask_dilate(gdf_engine* e, const uint32_t* in, uint32_t* out, uint32_t W, uint32_t H,
                     uint32_t F, int as_written) {
     ENGINE_OR_FAIL(e);

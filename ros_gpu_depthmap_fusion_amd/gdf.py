@@ -156,7 +156,7 @@ EXPORTED = [
     "gdf_run_depth_stream_alternating",
     "gdf_next_frame_in_batch", "gdf_get_batch_ranges", "gdf_download_batch_occupancy_grid",
     "gdf_mask_dilate", "gdf_transform_points", "gdf_add_halo_depthmap_device",
-    "gdf_partition_points", "gdf_voxelize_points", "gdf_partition_runs", "gdf_voxelize_runs", "gdf_voxelize_runs_marked", "gdf_voxelize_runs_recv", "gdf_set_partition_marks", "gdf_set_emit_partition", "gdf_set_partition_segments", "gdf_last_sort_items", "gdf_get_stream",
+    "gdf_partition_points", "gdf_voxelize_points", "gdf_partition_runs", "gdf_voxelize_runs", "gdf_voxelize_runs_marked", "gdf_voxelize_runs_recv", "gdf_set_partition_marks", "gdf_set_emit_partition", "gdf_set_partition_segments", "gdf_last_sort_items", "gdf_last_group_queue", "gdf_get_stream",
     "gdf_get_graph_stats", "gdf_get_slot", "gdf_select_slot", "gdf_build_info", "gdf_get_tuning",
     "gdf_get_frame_kernels",
     "gdf_download_frame", "gdf_set_slot_streams",
@@ -275,6 +275,7 @@ def load_library(path: str = LIB_PATH):
         "gdf_get_batch_ranges": (i32, [vp, vp, vp, u32, P(u32)]),
         "gdf_download_batch_occupancy_grid": (i32, [vp, u32, vp, u64]),
         "gdf_last_sort_items": (i32, [vp, P(u32), P(i32)]),
+        "gdf_last_group_queue": (i32, [vp, P(u32), P(u32)]),
         "gdf_get_stream": (i32, [vp, P(vp)]),
         "gdf_get_graph_stats": (i32, [vp, P(u64), P(u64)]),
         "gdf_get_slot": (i32, [vp, P(i32)]),
@@ -1081,6 +1082,13 @@ class GPUDepthmapFusion:
         n, r = C.c_uint32(0), C.c_int(0)
         self._check(self._lib.gdf_last_sort_items(self._h, C.byref(n), C.byref(r)))
         return n.value, bool(r.value)
+
+    def last_group_queue(self):
+        """(queued, huge): the voxel groups the last voxelize over sorted runs handed from
+        k_group_runs to k_group_runs_big, below and in the huge region (instrumentation)."""
+        q, h = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.gdf_last_group_queue(self._h, C.byref(q), C.byref(h)))
+        return q.value, h.value
 
     def processFramePrepared(self, p: FrameParams) -> FrameResult:
         """processFrame with parameters already converted by ComponentParams.to_c (a stream of
