@@ -436,6 +436,24 @@ public:
             m_objectPointIndex.data(), total, m_objectPointStarts.data(), m_objectVoxels.data(),
             nobj + 1));
     }
+    // The moments of every object's own points (no reference counterpart; include/gdf_segment.h,
+    // "per-object moments"): after objectPoints(), on the voxel grid of computeVoxelCoords, per
+    // object the count, the tight bounds and the first and second sums of its grouped points in
+    // 1/256 cell units (m_objectMoments, computed on the GPU), and from them the centroid, the
+    // covariance and the bounds in world units (m_objectShapes; NaN for an object without points).
+    void objectMoments() {
+        if (!seg_) throw std::runtime_error("objectMoments before objectSegmentation");
+        uint32_t gs[3] = {0, 0, 0};
+        uint64_t cells = 0;
+        check(gdf_get_grid_size(h_, gs, &cells));
+        check(gdf_seg_object_moments(seg_, lo_, cs_, gs));
+        uint32_t nobj = 0;
+        check(gdf_seg_get_object_points(seg_, &nobj, nullptr));
+        m_objectMoments.resize(nobj);
+        m_objectShapes.resize(nobj);
+        check(gdf_seg_download_object_moments(seg_, m_objectMoments.data(), nobj));  // (nobj >= 1)
+        check(gdf_obj_shapes_from_moments(m_objectMoments.data(), nobj, lo_, cs_, m_objectShapes.data()));
+    }
     // objectTracking (:2727-2944): associates m_ccObjects with m_ccObjectTracks
     void objectTracking(float min_area) { object_tracking(m_ccObjects, m_ccObjectTracks, min_area); }
 
@@ -489,6 +507,9 @@ public:
     std::vector<uint32_t> m_pointObjectIds;
     std::vector<vec4> m_points_objects;
     std::vector<uint32_t> m_objectPointIndex, m_objectPointStarts, m_objectVoxels;
+    // objectMoments: one record and one shape per object, in the order of m_objectVoxels
+    std::vector<gdf_obj_moments> m_objectMoments;
+    std::vector<gdf_obj_shape> m_objectShapes;
 
 private:
     // one CCObject from the GPU record + the contours (fusion.cpp:2371-2537)

@@ -174,6 +174,60 @@ int gdf_seg_set_profiling(gdf_segmenter* seg, int enable);
 int gdf_seg_get_object_points_times(gdf_segmenter* seg, float* ms, uint32_t capacity,
                                     uint32_t* count);
 
+/* ---- per-object moments of the grouped clouds -----------------------------------
+ *
+ * No reference counterpart; the rule is this library's specification.  Inputs: the grouped result
+ * of the last gdf_seg_group_points / gdf_seg_object_points (rows points[total], obj_start[nobj + 1],
+ * total a device word) and the grid of gdf_compute_voxel_coords: lower[3], cell[3] (f32), gs[3].
+ * For a row p and axis a, with S = GDF_OBJ_SUBDIV:
+ *   t[a] = (p[a] - lower[a]) / cell[a]     in f32, correctly rounded, not contracted (the
+ *                                          expression of computeVoxelCoords)
+ *   measured iff 0 <= t[a] && t[a] <= (float)gs[a] on all three axes (NaN fails)
+ *   q[a] = min((uint32)(t[a] * S), S * gs[a] - 1)       (the product is exact; truncation)
+ * so q[a] / S is the clamped voxel coordinate of every measured row.  Object o's record covers its
+ * rows [obj_start[o], obj_start[o + 1]); unmeasured rows add to `outside` only.  Integer sums:
+ * exact and independent of the order of the rows. */
+#define GDF_OBJ_SUBDIV 256u
+
+typedef struct gdf_obj_moments {
+    uint32_t count, outside;      /* measured rows; the other rows of the object        */
+    uint32_t qmin[3], qmax[3];    /* over measured rows; count == 0: 0xFFFFFFFF and 0   */
+    uint64_t sum[3];              /* sum of q[a]                                        */
+    uint64_t sum2[6];             /* sum of q[a] q[b] for xx, xy, xz, yy, yz, zz        */
+} gdf_obj_moments;
+
+/* Enqueued on the stream of the call that produced the grouped result, with no host wait (a
+ * workspace buffer that has to grow is reallocated).  GDF_ERR_ARG: a null pointer, a cell[a] that
+ * is not > 0, a grid_size[a] that is 0 or above 65536, and (256 max(grid_size) - 1)^2 * n_cap >=
+ * 2^64 with n_cap the capacity of the grouped result (below it no sum can wrap).  GDF_ERR_STATE:
+ * no grouped result (before any group call, or after a gdf_seg_label_* since the last one).
+ * Every refusal comes before the first launch and leaves an earlier result alone.  The records
+ * stay valid as long as the grouped result does. */
+int gdf_seg_object_moments(gdf_segmenter* seg, const float lower[3], const float cell[3],
+                           const uint32_t grid_size[3]);
+/* nobj records (waits); GDF_ERR_CAPACITY when capacity < nobj, GDF_ERR_STATE without records */
+int gdf_seg_download_object_moments(gdf_segmenter* seg, gdf_obj_moments* out, uint32_t capacity);
+/* the same on the device */
+int gdf_seg_get_device_object_moments(gdf_segmenter* seg, const gdf_obj_moments** moments);
+
+/* Centroid, covariance and bounds in world units from the records: a pure host function (no GPU,
+ * no handle).  In doubles, in exactly this order, with N = count, c_a = (double)cell[a] / 256.0,
+ * l_a = (double)lower[a]:
+ *   centroid[a]  = l_a + c_a * ((double)sum[a] / (double)N + 0.5)
+ *   cov[ab]      = ((double)(N sum2[ab] - sum[a] sum[b]) / ((double)N * (double)N)) * c_a * c_b
+ *                  (the numerator exact in 128-bit integers, converted once, to nearest even)
+ *   min_world[a] = l_a + c_a * (double)qmin[a]
+ *   max_world[a] = l_a + c_a * (double)(qmax[a] + 1)
+ * count == 0 gives NaN in every field.  cov in the order of sum2. */
+typedef struct gdf_obj_shape {
+    double centroid[3];
+    double cov[6];
+    double min_world[3], max_world[3];
+} gdf_obj_shape;
+
+int gdf_obj_shapes_from_moments(const gdf_obj_moments* m, uint32_t nobj, const float lower[3],
+                                const float cell[3], gdf_obj_shape* out);
+
 #ifdef __cplusplus
 }
 #endif

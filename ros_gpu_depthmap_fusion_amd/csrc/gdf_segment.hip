@@ -36,6 +36,7 @@
 #include "gdf.h"
 #include "gdf_segment.h"
 #include "gdf_kernels.hpp"
+#include "gdf_object_moments.hpp"
 #include "gdf_object_points.hpp"
 
 namespace {
@@ -899,6 +900,10 @@ struct gdf_segmenter {
         bool profiling = false;
         std::vector<hipEvent_t> ev;
         uint32_t nev = 0;                      // events the last call recorded
+        // the per-object moments of this grouped result (gdf_object_moments.hip); the partial
+        // table needs no clearing: every slot that is read was written by the same call
+        GpuBuf moments, om_partial;
+        bool om_valid = false;
     } op;
 };
 
@@ -1003,7 +1008,7 @@ void run_label_layers(gdf_segmenter* g, const uint8_t* grid, uint32_t W, uint32_
     g->have = false;  // (a failed call leaves no result behind)
     g->contours_read = false;
     g->merged_have = false;
-    g->op.valid = false;
+    g->op.valid = g->op.om_valid = false;
     if (!grid || W == 0 || H == 0 || L == 0) seg_fail(GDF_ERR_ARG, "empty grid");
     if (W > 65534 || H > 65534) seg_fail(GDF_ERR_ARG, "layers wider or taller than 65534 cells");
     const uint32_t BW = (W + 1) / 2, BH = (H + 1) / 2;
@@ -1608,7 +1613,7 @@ int gdf_seg_group_points(gdf_segmenter* g, const float* pts, const uint32_t* ids
         if (!pts || !ids) seg_fail(GDF_ERR_ARG, "group points: null argument");
         check_nobj(nobj);
         SEGCHK(hipSetDevice(g->device));
-        g->op.valid = false;
+        g->op.valid = g->op.om_valid = false;
         g->op.have_ids = false;
         StreamUse use(g, g->s());
         hipEvent_t* ev = op_events(g, nobj, g->s());
@@ -1636,7 +1641,7 @@ int gdf_seg_object_points(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) 
         const uint32_t nobj = g->nobj;
         check_nobj(nobj);
         gdf_segmenter::ObjectPoints& w = g->op;
-        w.valid = false;
+        w.valid = w.om_valid = false;
         w.have_ids = false;
         SEGCHK(w.ids.ensure((size_t)std::max(fp.cap, 1u) * 4));
         SEGCHK(w.voxels.ensure((size_t)nobj * 4));
@@ -1722,6 +1727,71 @@ int gdf_seg_get_device_object_points(gdf_segmenter* g, const uint32_t** ids, con
     if (obj_start) *obj_start = w.obj_start.as<const uint32_t>();
     if (voxels) *voxels = w.have_ids ? w.voxels.as<const uint32_t>() : nullptr;
     if (count) *count = w.words.as<const uint32_t>();
+    return GDF_OK;
+}
+
+// ---- per-object moments of the grouped clouds -----------------------------------
+int gdf_seg_object_moments(gdf_segmenter* g, const float lower[3], const float cell[3],
+                           const uint32_t gs[3]) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        // every refusal comes before the first launch
+        if (!lower || !cell || !gs) seg_fail(GDF_ERR_ARG, "object moments: null argument");
+        for (int a = 0; a < 3; ++a) {
+            if (!(cell[a] > 0.0f)) seg_fail(GDF_ERR_ARG, "object moments: a cell size that is not > 0");
+            if (gs[a] == 0 || gs[a] > gdf::kOmMaxGrid)
+                seg_fail(GDF_ERR_ARG, "object moments: a grid size of 0 or above 65536");
+        }
+        gdf_segmenter::ObjectPoints& w = g->op;
+        if (!w.valid) seg_fail(GDF_ERR_STATE, "object moments: no grouped points");
+        if (!gdf::om_sums_fit(gs, w.n_cap))
+            seg_fail(GDF_ERR_ARG, "object moments: the sums of this grid and capacity can pass 2^64");
+        SEGCHK(hipSetDevice(g->device));
+        const hipStream_t s = w.stream;
+        StreamUse use(g, s);
+        w.om_valid = false;
+        SEGCHK(w.moments.ensure((size_t)w.nobj * sizeof(gdf_obj_moments)));
+        SEGCHK(w.om_partial.ensure(gdf::om_partial_records(w.n_cap) * sizeof(gdf_obj_moments)));
+        gdf::ObjMomentArgs a{};
+        a.pts = w.out.as<const float4>();
+        a.obj_start = w.obj_start.as<const uint32_t>();
+        a.total = w.words.as<const uint32_t>();
+        a.n_cap = w.n_cap;
+        a.nobj = w.nobj;
+        for (int k = 0; k < 3; ++k) {
+            a.lower[k] = lower[k];
+            a.cell[k] = cell[k];
+            a.gs[k] = gs[k];
+        }
+        a.moments = w.moments.as<gdf_obj_moments>();
+        a.partial = w.om_partial.as<uint32_t>();
+        SEGCHK(gdf::launch_object_moments(a, s));
+        w.om_valid = true;
+    });
+}
+
+int gdf_seg_download_object_moments(gdf_segmenter* g, gdf_obj_moments* out, uint32_t cap) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        gdf_segmenter::ObjectPoints& w = g->op;
+        if (!out) seg_fail(GDF_ERR_ARG, "object moments: null argument");
+        if (!w.valid || !w.om_valid) seg_fail(GDF_ERR_STATE, "no object moments (call gdf_seg_object_moments)");
+        if (cap < w.nobj) seg_fail(GDF_ERR_CAPACITY, "object moments capacity too small");
+        SEGCHK(hipSetDevice(g->device));
+        SEGCHK(hipMemcpyAsync(out, w.moments.p, (size_t)w.nobj * sizeof(gdf_obj_moments),
+                              hipMemcpyDeviceToHost, w.stream));
+        SEGCHK(hipStreamSynchronize(w.stream));
+    });
+}
+
+int gdf_seg_get_device_object_moments(gdf_segmenter* g, const gdf_obj_moments** moments) {
+    if (!g || !moments) return GDF_ERR_ARG;
+    const gdf_segmenter::ObjectPoints& w = g->op;
+    if (!w.valid || !w.om_valid) {
+        gdf::set_last_error("no object moments (call gdf_seg_object_moments)");
+        return GDF_ERR_STATE;
+    }
+    *moments = w.moments.as<const gdf_obj_moments>();
     return GDF_OK;
 }
 

@@ -177,6 +177,9 @@ EXPORTED = [
     "gdf_seg_download_object_points",
     "gdf_seg_get_device_object_points", "gdf_seg_set_profiling",
     "gdf_seg_get_object_points_times",
+    # ... per-object moments of the grouped clouds
+    "gdf_seg_object_moments", "gdf_seg_download_object_moments",
+    "gdf_seg_get_device_object_moments", "gdf_obj_shapes_from_moments",
     # include/gdf_filter.h: the radius outlier filter
     "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
     "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
@@ -325,6 +328,10 @@ def load_library(path: str = LIB_PATH):
         "gdf_seg_get_device_object_points": (i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(vp)]),
         "gdf_seg_set_profiling": (i32, [vp, i32]),
         "gdf_seg_get_object_points_times": (i32, [vp, vp, u32, P(u32)]),
+        "gdf_seg_object_moments": (i32, [vp, vp, vp, vp]),
+        "gdf_seg_download_object_moments": (i32, [vp, vp, u32]),
+        "gdf_seg_get_device_object_moments": (i32, [vp, P(vp)]),
+        "gdf_obj_shapes_from_moments": (i32, [vp, u32, vp, vp, vp]),
         "gdf_radius_filter_plan": (i32, [P(RadiusFilterParams), vp, vp]),
         "gdf_radius_filter_points": (i32, [vp, vp, u32, P(RadiusFilterParams), vp, vp, vp]),
         "gdf_radius_filter": (i32, [vp, i32, P(RadiusFilterParams)]),
@@ -1102,6 +1109,26 @@ class GPUDepthmapFusion:
 # segmentation flags (include/gdf_segment.h)
 SEG_CONTOURS, SEG_CONNECTIONS, SEG_ALL = 1, 2, 3
 OBJ_NONE = 0xFFFFFFFF  # GDF_OBJ_NONE
+OBJ_SUBDIV = 256       # GDF_OBJ_SUBDIV
+# gdf_obj_moments (104 B) and gdf_obj_shape (120 B) as structured arrays
+OBJ_MOMENTS_DTYPE = np.dtype([("count", "<u4"), ("outside", "<u4"), ("qmin", "<u4", 3),
+                              ("qmax", "<u4", 3), ("sum", "<u8", 3), ("sum2", "<u8", 6)])
+OBJ_SHAPE_DTYPE = np.dtype([("centroid", "<f8", 3), ("cov", "<f8", 6), ("min_world", "<f8", 3),
+                            ("max_world", "<f8", 3)])
+assert OBJ_MOMENTS_DTYPE.itemsize == 104 and OBJ_SHAPE_DTYPE.itemsize == 120
+
+
+def obj_shapes_from_moments(moments, lower, cell, lib_path: str = LIB_PATH) -> np.ndarray:
+    """gdf_obj_shapes_from_moments: centroid, covariance (xx, xy, xz, yy, yz, zz) and bounds in world
+    units of every record, in doubles on the host (no GPU); count == 0 gives NaN."""
+    m = np.ascontiguousarray(moments, OBJ_MOMENTS_DTYPE).reshape(-1)
+    out = np.zeros(len(m), OBJ_SHAPE_DTYPE)
+    lib = load_library(lib_path)
+    rc = lib.gdf_obj_shapes_from_moments(_ptr(m), len(m), _ptr(_vec3(lower)), _ptr(_vec3(cell)),
+                                         _ptr(out))
+    if rc != GDF_OK:
+        raise GDFError(rc, (lib.gdf_last_error() or b"").decode())
+    return out
 
 
 class Segmenter:
@@ -1255,6 +1282,26 @@ class Segmenter:
         self._check(self._lib.gdf_seg_get_device_object_points(self._h, *[C.byref(x) for x in p]))
         keys = ("ids", "points", "index", "obj_start", "voxels", "count")
         return {k: (x.value or 0) for k, x in zip(keys, p)}
+
+    def object_moments(self, lower, cell, grid_size, download: bool = True):
+        """Per-object moments of the last grouped result on the grid (lower, cell, grid_size) of
+        computeVoxelCoords: a structured array [nobj] of OBJ_MOMENTS_DTYPE.  The call itself is
+        enqueued without a host wait; download=False skips the download (object_moments_device)."""
+        gs = np.ascontiguousarray(np.asarray(grid_size, dtype=np.uint32).reshape(3))
+        self._check(self._lib.gdf_seg_object_moments(self._h, _ptr(_vec3(lower)), _ptr(_vec3(cell)),
+                                                     _ptr(gs)))
+        return self.object_moments_results() if download else None
+
+    def object_moments_results(self) -> np.ndarray:
+        nobj, _ = self.object_points_counts()
+        out = np.zeros(nobj, OBJ_MOMENTS_DTYPE)
+        self._check(self._lib.gdf_seg_download_object_moments(self._h, _ptr(out), nobj))
+        return out
+
+    def object_moments_device(self) -> int:
+        p = C.c_void_p()
+        self._check(self._lib.gdf_seg_get_device_object_moments(self._h, C.byref(p)))
+        return p.value or 0
 
     def set_profiling(self, enable: bool):
         self._check(self._lib.gdf_seg_set_profiling(self._h, int(bool(enable))))
