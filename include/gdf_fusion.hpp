@@ -454,6 +454,36 @@ public:
         check(gdf_seg_download_object_moments(seg_, m_objectMoments.data(), nobj));  // (nobj >= 1)
         check(gdf_obj_shapes_from_moments(m_objectMoments.data(), nobj, lo_, cs_, m_objectShapes.data()));
     }
+    // The voxelized cloud by object (no reference counterpart; include/gdf_segment.h, "the voxel
+    // table"): after voxelize() and objectSegmentation().  Per row g of m_points_voxelized its cell
+    // (m_voxelCells), the number of points of m_points folded into it (m_voxelPointCounts, the weight
+    // of its mean) and its object id (m_voxelObjectIds); per point of m_points its voxelized row
+    // (m_pointVoxelIndex); and the voxelized rows of every object with at least max(min_voxels, 1)
+    // voxels grouped by object (object o's at [m_objectVoxelStarts[o], m_objectVoxelStarts[o + 1])
+    // in row order), each with its row index and its weight - computed on the GPU.  It replaces the
+    // grouped result of objectPoints() inside the segmenter: objectMoments() after it measures the
+    // grouped voxelized rows, every row counting once (unweighted).
+    void objectVoxels(uint32_t min_voxels = 0) {
+        if (!seg_) throw std::runtime_error("objectVoxels before objectSegmentation");
+        check(gdf_seg_object_voxels(seg_, h_, min_voxels));
+        uint32_t nobj = 0, total = 0, G = 0, n = 0;
+        check(gdf_seg_get_object_points(seg_, &nobj, &total));
+        check(gdf_seg_get_voxel_table(seg_, &G, &n));
+        m_voxelCells.resize(G);
+        m_voxelPointCounts.resize(G);
+        m_pointVoxelIndex.resize(n);
+        m_voxelObjectIds.resize(G);
+        m_voxels_objects.resize(total);
+        m_objectVoxelIndex.resize(total);
+        m_objectVoxelStarts.resize((size_t)nobj + 1);
+        m_objectVoxelWeights.resize(total);
+        check(gdf_seg_download_voxel_table(seg_, m_voxelCells.data(), m_voxelPointCounts.data(), G,
+                                           m_pointVoxelIndex.data(), n, m_objectVoxelWeights.data(),
+                                           total));
+        check(gdf_seg_download_object_points(
+            seg_, m_voxelObjectIds.data(), G, reinterpret_cast<float*>(m_voxels_objects.data()),
+            m_objectVoxelIndex.data(), total, m_objectVoxelStarts.data(), nullptr, nobj + 1));
+    }
     // objectTracking (:2727-2944): associates m_ccObjects with m_ccObjectTracks
     void objectTracking(float min_area) { object_tracking(m_ccObjects, m_ccObjectTracks, min_area); }
 
@@ -507,6 +537,12 @@ public:
     std::vector<uint32_t> m_pointObjectIds;
     std::vector<vec4> m_points_objects;
     std::vector<uint32_t> m_objectPointIndex, m_objectPointStarts, m_objectVoxels;
+    // objectVoxels: per row of m_points_voxelized its cell, point count and object id; per point of
+    // m_points its voxelized row (GDF_VOX_NONE: outside the grid); the kept voxelized rows grouped
+    // by object, their indices into m_points_voxelized, the objects' ranges and the rows' weights
+    std::vector<uint32_t> m_voxelCells, m_voxelPointCounts, m_pointVoxelIndex, m_voxelObjectIds;
+    std::vector<vec4> m_voxels_objects;
+    std::vector<uint32_t> m_objectVoxelIndex, m_objectVoxelStarts, m_objectVoxelWeights;
     // objectMoments: one record and one shape per object, in the order of m_objectVoxels
     std::vector<gdf_obj_moments> m_objectMoments;
     std::vector<gdf_obj_shape> m_objectShapes;

@@ -124,7 +124,7 @@ int gdf_seg_get_device_results(gdf_segmenter* seg, const uint16_t** labels, cons
  * (the workspace is grow-only: a steady stream of frames stops growing).  The input count may be
  * a device word (count_device != NULL: n = min(*count_device, n_cap)); rows at and beyond n are
  * neither read nor written.  Results stay valid until the next gdf_seg_label_* or the next
- * gdf_seg_group_points / gdf_seg_object_points.
+ * gdf_seg_group_points / gdf_seg_object_points / gdf_seg_object_voxels (below).
  * Streams: the labelling and these calls may run on different streams (the segmenter's and an
  * engine's), in any order; a call whose stream differs from the previous call's waits on the
  * device for that call's work, so no host wait is needed between them. */
@@ -227,6 +227,69 @@ typedef struct gdf_obj_shape {
 
 int gdf_obj_shapes_from_moments(const gdf_obj_moments* m, uint32_t nobj, const float lower[3],
                                 const float cell[3], gdf_obj_shape* out);
+
+/* ---- the voxel table of a list of cells; object ids for the voxelized cloud -----
+ *
+ * No reference counterpart; the rule is this library's specification.  Inputs: cells[n] (u32),
+ * num_cells = C, and n as a value or a device word (count_device != NULL: n = min(*count_device,
+ * n_cap)).
+ *   outside      a row with cells[i] >= C marks nothing, counts nowhere and gets
+ *                point_voxel[i] = GDF_VOX_NONE
+ *   vox_cells    vox_cells[G]: the distinct cells below C, ascending; G is a device word too
+ *   point_voxel  point_voxel[i] = the index of cells[i] in vox_cells
+ *   vox_counts   vox_counts[g] = the number of rows with point_voxel == g
+ * Rows at and beyond n are neither read nor written.  All outputs are integers and no output
+ * depends on an order of execution: the result is exact.
+ * The voxelize of gdf.h emits one row per distinct key of the frame's voxel coords, in ascending
+ * key order, so with cells = the frame's coords and C = the grid's cell count, voxel g of the table
+ * is voxelized row g: vox_counts[g] is the number of compacted points behind that row (the weight of
+ * its mean) and point_voxel[i] is the voxelized row that compacted point i was folded into.
+ * C is bounded by 2^28 cells: the table marks one bit per cell, a bitmap of at most 32 MB, which
+ * (unlike the workspace of the object points) every call clears before its marks.
+ * The workspace is grow-only, as the object points' is.  Results stay valid until the next
+ * gdf_seg_label_*, gdf_seg_voxel_table or gdf_seg_object_voxels. */
+#define GDF_VOX_NONE 0xFFFFFFFFu
+
+/* the rule on any device array, on the segmenter's stream; needs no labelling.  GDF_ERR_ARG: a null
+ * cells pointer, num_cells == 0, num_cells > 2^28.  n_cap == 0 succeeds with G = 0.  A refusal
+ * leaves an earlier result readable. */
+int gdf_seg_voxel_table(gdf_segmenter* seg, const uint32_t* cells_device, uint32_t n_cap,
+                        const uint32_t* count_device, uint32_t num_cells);
+
+/* Object ids for the engine's voxelized cloud, on the engine's stream: the table of the frame's
+ * voxel coords; ids[g] = the object id of vox_cells[g] (the id rule above, G of them); voxels and
+ * keep as gdf_seg_object_points computes them; the engine's voxelized rows partitioned by those
+ * ids; weights[j] = vox_counts[index[j]].  The grouped result is THE grouped result of the
+ * segmenter: it replaces an earlier gdf_seg_group_points / gdf_seg_object_points result, and
+ * gdf_seg_get_object_points, gdf_seg_download_object_points, gdf_seg_get_device_object_points and
+ * gdf_seg_object_moments work on it unchanged, with ids of G entries and index[j] a voxel index
+ * (a voxelized row).  gdf_seg_object_moments on it is unweighted: every voxelized row counts once.
+ * The rows grouped are min(G, the voxelize's own device count) of the engine's voxelized rows: the
+ * two counts are equal for a frame's own coords, and the minimum keeps any mismatch inside the rows
+ * the voxelize wrote.
+ * Refusals, all before the first launch: what gdf_seg_object_points refuses, and GDF_ERR_STATE
+ * before the frame's voxelize.  No host wait apart from the one for nobj after a labelling. */
+int gdf_seg_object_voxels(gdf_segmenter* seg, gdf_engine* engine, uint32_t min_voxels);
+
+/* G and n of the last table (waits) */
+int gdf_seg_get_voxel_table(gdf_segmenter* seg, uint32_t* num_voxels, uint32_t* n);
+/* Downloads (wait); every pointer may be NULL.  vox_cells and vox_counts: G words (vox_capacity);
+ * point_voxel: n words (point_capacity); weights: the kept total of the grouped voxel rows
+ * (weights_capacity), GDF_ERR_STATE unless the table is gdf_seg_object_voxels' and its grouped
+ * result still stands.  GDF_ERR_CAPACITY when a capacity is too small. */
+int gdf_seg_download_voxel_table(gdf_segmenter* seg, uint32_t* vox_cells, uint32_t* vox_counts,
+                                 uint32_t vox_capacity, uint32_t* point_voxel,
+                                 uint32_t point_capacity, uint32_t* weights,
+                                 uint32_t weights_capacity);
+/* the same on the device; weights is NULL where the download refuses it; count_device: G */
+int gdf_seg_get_device_voxel_table(gdf_segmenter* seg, const uint32_t** vox_cells,
+                                   const uint32_t** vox_counts, const uint32_t** point_voxel,
+                                   const uint32_t** weights, const uint32_t** count_device);
+/* With gdf_seg_set_profiling on, the last table call's times in milliseconds (waits): [clear],
+ * [mark], [row sums + scan], [expand], [rank]: 5 values; after gdf_seg_object_voxels also
+ * [ids + sizes], [group], [weights]: 8 values. */
+int gdf_seg_get_voxel_table_times(gdf_segmenter* seg, float* ms, uint32_t capacity,
+                                  uint32_t* count);
 
 #ifdef __cplusplus
 }

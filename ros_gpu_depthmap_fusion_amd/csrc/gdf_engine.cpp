@@ -30,6 +30,7 @@
 #include "gdf_kernels.hpp"
 #include "gdf_filter.hpp"
 #include "gdf_object_points.hpp"
+#include "gdf_voxel_table.hpp"
 
 using namespace gdf;
 
@@ -2312,6 +2313,19 @@ int gdf::engine_frame_points(gdf_engine* e, FramePoints* out) {
         std::memcpy(out->gs, e->gs, 12);
         out->stream = e->s();
         out->device = e->device;
+    });
+}
+
+// ... and its voxelized rows with their device count, for gdf_seg_object_voxels (which takes the
+// coords and the refusals of the compacted side from engine_frame_points first)
+int gdf::engine_frame_voxels(gdf_engine* e, FrameVoxels* out) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "object voxels before the frame's voxelize");
+        out->vox = q.d_vox.as<float4>();
+        out->n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
+        out->cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, 0xFFFFFFFFu);
     });
 }
 

@@ -38,6 +38,7 @@
 #include "gdf_kernels.hpp"
 #include "gdf_object_moments.hpp"
 #include "gdf_object_points.hpp"
+#include "gdf_voxel_table.hpp"
 
 namespace {
 
@@ -905,6 +906,19 @@ struct gdf_segmenter {
         GpuBuf moments, om_partial;
         bool om_valid = false;
     } op;
+    // the voxel table (gdf_voxel_table.hip): grow-only workspace and results.  The bitmap has to be
+    // zero before the marks (the call clears it); nothing else has to be clean between calls.
+    // words: {G, n}.
+    struct VoxelTable {
+        GpuBuf bitmap, row_rank, sums, word_rank, words, vox_cells, vox_counts, point_voxel, weights;
+        bool valid = false;
+        bool n_on_device = false;   // words[1] holds n (else n == n_cap)
+        bool have_weights = false;  // weights belong to the standing grouped result (object voxels)
+        uint32_t n_cap = 0;
+        hipStream_t stream = nullptr;
+        std::vector<hipEvent_t> ev;
+        uint32_t nev = 0;           // events the last call recorded
+    } vt;
 };
 
 namespace {
@@ -1009,6 +1023,7 @@ void run_label_layers(gdf_segmenter* g, const uint8_t* grid, uint32_t W, uint32_
     g->contours_read = false;
     g->merged_have = false;
     g->op.valid = g->op.om_valid = false;
+    g->vt.valid = g->vt.have_weights = false;
     if (!grid || W == 0 || H == 0 || L == 0) seg_fail(GDF_ERR_ARG, "empty grid");
     if (W > 65534 || H > 65534) seg_fail(GDF_ERR_ARG, "layers wider or taller than 65534 cells");
     const uint32_t BW = (W + 1) / 2, BH = (H + 1) / 2;
@@ -1180,6 +1195,7 @@ int gdf_seg_destroy(gdf_segmenter* g) {
     if (g->ev_contours) (void)hipEventDestroy(g->ev_contours);
     if (g->ev_last) (void)hipEventDestroy(g->ev_last);
     for (hipEvent_t ev : g->op.ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : g->vt.ev) (void)hipEventDestroy(ev);
     delete g;
     return GDF_OK;
 }
@@ -1458,6 +1474,27 @@ gdf::ObjIdArgs id_args(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap,
     return a;
 }
 
+// steps 1 to 3 of §12 on (cells, n) into op.ids, op.voxels and op.keep, on s: the ids of the cells,
+// the objects' voxel counts and the keep flags (gdf_seg_object_points: the frame's coords;
+// gdf_seg_object_voxels: the table's vox_cells)
+void object_ids_and_sizes(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap,
+                          const uint32_t* n_dev, uint32_t nobj, uint32_t min_voxels, hipStream_t s) {
+    gdf_segmenter::ObjectPoints& w = g->op;
+    SEGCHK(gdf::launch_object_ids(id_args(g, cells, n_cap, n_dev, w.ids.as<uint32_t>()), s));
+    SEGCHK(hipMemsetAsync(w.voxels.p, 0, (size_t)nobj * 4, s));
+    gdf::ObjSizeArgs z{};
+    z.stats5 = g->stats5.as<const int32_t>();
+    z.merged = g->mout.as<const uint32_t>();
+    z.lstart = g->lstart.as<const uint32_t>();
+    z.L = g->L;
+    z.T = g->total;
+    z.nobj = nobj;
+    z.min_voxels = min_voxels;
+    z.voxels = w.voxels.as<uint32_t>();
+    z.keep = w.keep.as<uint8_t>();
+    SEGCHK(gdf::launch_object_sizes(z, s));
+}
+
 // {total, n} of the last call (waits)
 void op_counts(gdf_segmenter* g, uint32_t* total, uint32_t* n) {
     gdf_segmenter::ObjectPoints& w = g->op;
@@ -1467,6 +1504,84 @@ void op_counts(gdf_segmenter* g, uint32_t* total, uint32_t* n) {
     SEGCHK(hipStreamSynchronize(w.stream));
     *total = std::min(h[0], w.n_cap);
     *n = w.n_on_device ? std::min(h[1], w.n_cap) : w.n_cap;
+}
+
+// ---- the voxel table ---------------------------------------------------------------
+constexpr uint32_t kVtExtraEvents = 3;  // object voxels: after the ids + sizes, the group, the weights
+
+void check_num_cells(uint64_t C) {
+    if (C == 0) seg_fail(GDF_ERR_ARG, "voxel table: no cells");
+    if (C > gdf::kVtMaxCells) seg_fail(GDF_ERR_ARG, "voxel table: more than 2^28 cells");
+}
+
+hipEvent_t* vt_events(gdf_segmenter* g) {
+    gdf_segmenter::VoxelTable& t = g->vt;
+    t.nev = 0;
+    if (!g->op.profiling) return nullptr;
+    while (t.ev.size() < gdf::kVtEvents + kVtExtraEvents) {
+        hipEvent_t ev;
+        SEGCHK(hipEventCreate(&ev));
+        t.ev.push_back(ev);
+    }
+    return t.ev.data();
+}
+
+// the table of (cells, n) into the segmenter's buffers, on s
+// (a voxel has a row and a cell of its own, so G <= min(n_cap, C): the per-voxel arrays hold that
+// many words).  limit_dev != nullptr: words[2] = min(G, *limit_dev), else G.
+void voxel_table(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap, const uint32_t* n_dev,
+                 uint32_t C, const uint32_t* limit_dev, hipStream_t s, hipEvent_t* ev) {
+    gdf_segmenter::VoxelTable& t = g->vt;
+    const size_t nb = std::max(n_cap, 1u);
+    const uint32_t vox_cap = std::min(n_cap, C);
+    SEGCHK(t.words.ensure(256));
+    SEGCHK(t.vox_cells.ensure((size_t)std::max(vox_cap, 1u) * 4));
+    SEGCHK(t.vox_counts.ensure((size_t)std::max(vox_cap, 1u) * 4));
+    SEGCHK(t.point_voxel.ensure(nb * 4));
+    t.n_cap = n_cap;
+    t.stream = s;
+    t.n_on_device = n_cap != 0 && n_dev != nullptr;
+    if (n_cap == 0) {  // G = 0, nothing to launch
+        SEGCHK(hipMemsetAsync(t.words.p, 0, 12, s));
+        t.valid = true;
+        return;
+    }
+    SEGCHK(t.bitmap.ensure((size_t)gdf::vt_words(C) * 4));
+    SEGCHK(t.row_rank.ensure(((size_t)gdf::vt_rows(C) + 1) * 4));
+    SEGCHK(t.sums.ensure(gdf::vt_scan_words(C) * 4));
+    SEGCHK(t.word_rank.ensure((size_t)gdf::vt_words(C) * 4));
+    if (n_dev)
+        SEGCHK(hipMemcpyAsync(t.words.as<uint32_t>() + 1, n_dev, 4, hipMemcpyDeviceToDevice, s));
+    gdf::VoxTableArgs a{};
+    a.cells = cells;
+    a.n_dev = n_dev;
+    a.n_cap = n_cap;
+    a.num_cells = C;
+    a.bitmap = t.bitmap.as<uint32_t>();
+    a.row_rank = t.row_rank.as<uint32_t>();
+    a.sums = t.sums.as<uint32_t>();
+    a.word_rank = t.word_rank.as<uint32_t>();
+    a.G = t.words.as<uint32_t>();
+    a.limit_dev = limit_dev;
+    a.limited = t.words.as<uint32_t>() + 2;
+    a.vox_cap = vox_cap;
+    a.vox_cells = t.vox_cells.as<uint32_t>();
+    a.vox_counts = t.vox_counts.as<uint32_t>();
+    a.point_voxel = t.point_voxel.as<uint32_t>();
+    SEGCHK(gdf::launch_voxel_table(a, s, ev));
+    if (ev) t.nev = gdf::kVtEvents;
+    t.valid = true;
+}
+
+// {G, n} of the last table (waits)
+void vt_counts(gdf_segmenter* g, uint32_t* G, uint32_t* n) {
+    gdf_segmenter::VoxelTable& t = g->vt;
+    if (!t.valid) seg_fail(GDF_ERR_STATE, "no voxel table (call gdf_seg_voxel_table)");
+    uint32_t h[2] = {0, 0};
+    SEGCHK(hipMemcpyAsync(h, t.words.p, 8, hipMemcpyDeviceToHost, t.stream));
+    SEGCHK(hipStreamSynchronize(t.stream));
+    *n = t.n_on_device ? std::min(h[1], t.n_cap) : t.n_cap;
+    *G = std::min(h[0], *n);
 }
 
 }  // namespace
@@ -1615,6 +1730,7 @@ int gdf_seg_group_points(gdf_segmenter* g, const float* pts, const uint32_t* ids
         SEGCHK(hipSetDevice(g->device));
         g->op.valid = g->op.om_valid = false;
         g->op.have_ids = false;
+        g->vt.have_weights = false;  // (they belong to the grouped result this call replaces)
         StreamUse use(g, g->s());
         hipEvent_t* ev = op_events(g, nobj, g->s());
         group_points(g, reinterpret_cast<const float4*>(pts), ids, n_cap, n_dev, nobj, keep, g->s(), ev);
@@ -1643,23 +1759,12 @@ int gdf_seg_object_points(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) 
         gdf_segmenter::ObjectPoints& w = g->op;
         w.valid = w.om_valid = false;
         w.have_ids = false;
+        g->vt.have_weights = false;
         SEGCHK(w.ids.ensure((size_t)std::max(fp.cap, 1u) * 4));
         SEGCHK(w.voxels.ensure((size_t)nobj * 4));
         SEGCHK(w.keep.ensure(nobj));
         hipEvent_t* ev = op_events(g, nobj, s);
-        SEGCHK(gdf::launch_object_ids(id_args(g, fp.coords, fp.cap, fp.n_dev, w.ids.as<uint32_t>()), s));
-        SEGCHK(hipMemsetAsync(w.voxels.p, 0, (size_t)nobj * 4, s));
-        gdf::ObjSizeArgs z{};
-        z.stats5 = g->stats5.as<const int32_t>();
-        z.merged = g->mout.as<const uint32_t>();
-        z.lstart = g->lstart.as<const uint32_t>();
-        z.L = g->L;
-        z.T = g->total;
-        z.nobj = nobj;
-        z.min_voxels = min_voxels;
-        z.voxels = w.voxels.as<uint32_t>();
-        z.keep = w.keep.as<uint8_t>();
-        SEGCHK(gdf::launch_object_sizes(z, s));
+        object_ids_and_sizes(g, fp.coords, fp.cap, fp.n_dev, nobj, min_voxels, s);
         group_points(g, fp.pts, w.ids.as<const uint32_t>(), fp.cap, fp.n_dev, nobj,
                      w.keep.as<const uint8_t>(), s, ev);
         w.have_ids = true;
@@ -1793,6 +1898,149 @@ int gdf_seg_get_device_object_moments(gdf_segmenter* g, const gdf_obj_moments** 
     }
     *moments = w.moments.as<const gdf_obj_moments>();
     return GDF_OK;
+}
+
+// ---- the voxel table; object ids for the voxelized cloud ---------------------------
+int gdf_seg_voxel_table(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap, const uint32_t* n_dev,
+                        uint32_t C) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        if (!cells) seg_fail(GDF_ERR_ARG, "voxel table: null argument");
+        check_num_cells(C);
+        SEGCHK(hipSetDevice(g->device));
+        g->vt.valid = g->vt.have_weights = false;
+        StreamUse use(g, g->s());
+        voxel_table(g, cells, n_cap, n_dev, C, nullptr, g->s(), vt_events(g));
+    });
+}
+
+int gdf_seg_object_voxels(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) {
+    if (!g || !e) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        // every refusal comes before the first launch
+        need_connections(g);
+        gdf::FramePoints fp{};
+        int rc = gdf::engine_frame_points(e, &fp);
+        if (rc != GDF_OK) seg_fail(rc, gdf_last_error());
+        gdf::FrameVoxels fv{};
+        rc = gdf::engine_frame_voxels(e, &fv);
+        if (rc != GDF_OK) seg_fail(rc, gdf_last_error());
+        if (fp.gs[0] != g->W || fp.gs[1] != g->H || fp.gs[2] != g->L)
+            seg_fail(GDF_ERR_STATE, "object voxels: the labelled grid is not the engine's grid");
+        if (fp.device != g->device)
+            seg_fail(GDF_ERR_STATE, "object voxels: the engine is on another device");
+        const uint64_t C = (uint64_t)g->W * g->H * g->L;
+        check_num_cells(C);
+        SEGCHK(hipSetDevice(g->device));
+        const hipStream_t s = fp.stream;
+        StreamUse use(g, s);
+        ensure_merged(g, s);  // (the one wait: nobj sizes the object tables)
+        const uint32_t nobj = g->nobj;
+        check_nobj(nobj);
+        gdf_segmenter::ObjectPoints& w = g->op;
+        gdf_segmenter::VoxelTable& t = g->vt;
+        w.valid = w.om_valid = false;
+        w.have_ids = false;
+        w.nev = 0;
+        t.valid = t.have_weights = false;
+        // a voxel has a row and a cell, so the table holds at most min(fp.cap, C) voxels; the
+        // grouped rows are the engine's voxelized rows, min(G, the voxelize's own count) of them
+        // (the two are equal; the minimum keeps a mismatch from reading rows that were not written)
+        const uint32_t gcap = std::min(fp.cap, (uint32_t)C);
+        const uint32_t vcap = std::min(gcap, fv.cap);
+        SEGCHK(w.ids.ensure((size_t)std::max(gcap, 1u) * 4));
+        SEGCHK(w.voxels.ensure((size_t)nobj * 4));
+        SEGCHK(w.keep.ensure(nobj));
+        SEGCHK(t.weights.ensure((size_t)std::max(vcap, 1u) * 4));
+        hipEvent_t* ev = vt_events(g);
+        voxel_table(g, fp.coords, fp.cap, fp.n_dev, (uint32_t)C, fv.n_dev, s, ev);
+        if (fp.cap == 0) ev = nullptr;  // (no passes, no times)
+        const uint32_t* G = t.words.as<const uint32_t>();
+        object_ids_and_sizes(g, t.vox_cells.as<const uint32_t>(), gcap, G, nobj, min_voxels, s);
+        if (ev) SEGCHK(hipEventRecord(ev[gdf::kVtEvents], s));
+        group_points(g, fv.vox, w.ids.as<const uint32_t>(), vcap, G + 2, nobj, w.keep.as<const uint8_t>(),
+                     s, nullptr);
+        w.have_ids = true;
+        if (ev) SEGCHK(hipEventRecord(ev[gdf::kVtEvents + 1], s));
+        SEGCHK(gdf::launch_voxel_weights(t.vox_counts.as<const uint32_t>(), w.index.as<const uint32_t>(),
+                                         w.words.as<const uint32_t>(), vcap, t.weights.as<uint32_t>(), s));
+        if (ev) {
+            SEGCHK(hipEventRecord(ev[gdf::kVtEvents + 2], s));
+            t.nev = gdf::kVtEvents + kVtExtraEvents;
+        }
+        t.have_weights = true;
+    });
+}
+
+int gdf_seg_get_voxel_table(gdf_segmenter* g, uint32_t* num_voxels, uint32_t* n) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        uint32_t G, nn;
+        vt_counts(g, &G, &nn);
+        if (num_voxels) *num_voxels = G;
+        if (n) *n = nn;
+    });
+}
+
+int gdf_seg_download_voxel_table(gdf_segmenter* g, uint32_t* vox_cells, uint32_t* vox_counts,
+                                 uint32_t vox_cap, uint32_t* point_voxel, uint32_t point_cap,
+                                 uint32_t* weights, uint32_t weights_cap) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        gdf_segmenter::VoxelTable& t = g->vt;
+        uint32_t G, n, total = 0, nrows = 0;
+        vt_counts(g, &G, &n);
+        if (weights) {
+            if (!t.have_weights || !g->op.valid)
+                seg_fail(GDF_ERR_STATE, "voxel table: no weights (call gdf_seg_object_voxels)");
+            op_counts(g, &total, &nrows);
+        }
+        if ((vox_cells || vox_counts) && vox_cap < G) seg_fail(GDF_ERR_CAPACITY, "voxel capacity too small");
+        if (point_voxel && point_cap < n) seg_fail(GDF_ERR_CAPACITY, "point_voxel capacity too small");
+        if (weights && weights_cap < total) seg_fail(GDF_ERR_CAPACITY, "weights capacity too small");
+        const hipStream_t s = t.stream;
+        if (vox_cells && G) SEGCHK(hipMemcpyAsync(vox_cells, t.vox_cells.p, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+        if (vox_counts && G) SEGCHK(hipMemcpyAsync(vox_counts, t.vox_counts.p, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+        if (point_voxel && n)
+            SEGCHK(hipMemcpyAsync(point_voxel, t.point_voxel.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        if (weights && total)
+            SEGCHK(hipMemcpyAsync(weights, t.weights.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+        SEGCHK(hipStreamSynchronize(s));
+    });
+}
+
+int gdf_seg_get_device_voxel_table(gdf_segmenter* g, const uint32_t** vox_cells, const uint32_t** vox_counts,
+                                   const uint32_t** point_voxel, const uint32_t** weights,
+                                   const uint32_t** count) {
+    if (!g) return GDF_ERR_ARG;
+    const gdf_segmenter::VoxelTable& t = g->vt;
+    if (!t.valid) {
+        gdf::set_last_error("no voxel table (call gdf_seg_voxel_table)");
+        return GDF_ERR_STATE;
+    }
+    if (vox_cells) *vox_cells = t.vox_cells.as<const uint32_t>();
+    if (vox_counts) *vox_counts = t.vox_counts.as<const uint32_t>();
+    if (point_voxel) *point_voxel = t.point_voxel.as<const uint32_t>();
+    if (weights) *weights = t.have_weights && g->op.valid ? t.weights.as<const uint32_t>() : nullptr;
+    if (count) *count = t.words.as<const uint32_t>();
+    return GDF_OK;
+}
+
+int gdf_seg_get_voxel_table_times(gdf_segmenter* g, float* ms, uint32_t cap, uint32_t* count) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        SEGCHK(hipSetDevice(g->device));
+        gdf_segmenter::VoxelTable& t = g->vt;
+        if (!t.valid || t.nev < 2) seg_fail(GDF_ERR_STATE, "no profiled voxel-table call");
+        const uint32_t n = t.nev - 1;
+        if (count) *count = n;
+        if (!ms) return;
+        if (cap < n) seg_fail(GDF_ERR_CAPACITY, "times capacity too small");
+        SEGCHK(hipEventSynchronize(t.ev[t.nev - 1]));
+        for (uint32_t k = 0; k < n; ++k) SEGCHK(hipEventElapsedTime(&ms[k], t.ev[k], t.ev[k + 1]));
+    });
 }
 
 int gdf_seg_set_profiling(gdf_segmenter* g, int enable) {

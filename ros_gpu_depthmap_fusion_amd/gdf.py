@@ -180,6 +180,10 @@ EXPORTED = [
     # ... per-object moments of the grouped clouds
     "gdf_seg_object_moments", "gdf_seg_download_object_moments",
     "gdf_seg_get_device_object_moments", "gdf_obj_shapes_from_moments",
+    # ... the voxel table and object ids for the voxelized cloud
+    "gdf_seg_voxel_table", "gdf_seg_object_voxels", "gdf_seg_get_voxel_table",
+    "gdf_seg_download_voxel_table", "gdf_seg_get_device_voxel_table",
+    "gdf_seg_get_voxel_table_times",
     # include/gdf_filter.h: the radius outlier filter
     "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
     "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
@@ -331,6 +335,12 @@ def load_library(path: str = LIB_PATH):
         "gdf_seg_object_moments": (i32, [vp, vp, vp, vp]),
         "gdf_seg_download_object_moments": (i32, [vp, vp, u32]),
         "gdf_seg_get_device_object_moments": (i32, [vp, P(vp)]),
+        "gdf_seg_voxel_table": (i32, [vp, vp, u32, vp, u32]),
+        "gdf_seg_object_voxels": (i32, [vp, vp, u32]),
+        "gdf_seg_get_voxel_table": (i32, [vp, P(u32), P(u32)]),
+        "gdf_seg_download_voxel_table": (i32, [vp, vp, vp, u32, vp, u32, vp, u32]),
+        "gdf_seg_get_device_voxel_table": (i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]),
+        "gdf_seg_get_voxel_table_times": (i32, [vp, vp, u32, P(u32)]),
         "gdf_obj_shapes_from_moments": (i32, [vp, u32, vp, vp, vp]),
         "gdf_radius_filter_plan": (i32, [P(RadiusFilterParams), vp, vp]),
         "gdf_radius_filter_points": (i32, [vp, vp, u32, P(RadiusFilterParams), vp, vp, vp]),
@@ -1302,6 +1312,59 @@ class Segmenter:
         p = C.c_void_p()
         self._check(self._lib.gdf_seg_get_device_object_moments(self._h, C.byref(p)))
         return p.value or 0
+
+    def voxel_table(self, cells_ptr: int, n_cap: int, num_cells: int, count_ptr: int = 0):
+        """The voxel table of a device u32 array of cell indices (count_ptr: a device word holding
+        n, 0: n_cap): the distinct cells below num_cells in ascending order, the rows of each and
+        every row's voxel index; read it with voxel_table_results().  Needs no labelling."""
+        self._check(self._lib.gdf_seg_voxel_table(
+            self._h, C.c_void_p(cells_ptr), n_cap, C.c_void_p(count_ptr or None), num_cells))
+
+    def object_voxels(self, engine: "GPUDepthmapFusion", min_voxels: int = 0):
+        """The table of the engine's voxel coords, an object id per voxelized row and the
+        voxelized rows grouped by object, on the engine's stream (after voxelize and
+        label_engine_grid with SEG_CONNECTIONS).  The grouped rows are read with
+        object_points_results() (ids and index address voxelized rows), the table and the grouped
+        rows' weights with voxel_table_results()."""
+        self._check(self._lib.gdf_seg_object_voxels(self._h, engine._h, min_voxels))
+
+    def voxel_table_counts(self):
+        """(G, n) of the last table (waits)."""
+        G, n = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.gdf_seg_get_voxel_table(self._h, C.byref(G), C.byref(n)))
+        return G.value, n.value
+
+    def voxel_table_results(self) -> dict:
+        """vox_cells [G], vox_counts [G], point_voxel [n], num_voxels, n and - after object_voxels,
+        while its grouped result stands - weights [the grouped rows' total]."""
+        G, n = self.voxel_table_counts()
+        r = {"num_voxels": G, "n": n, "vox_cells": np.zeros(G, np.uint32),
+             "vox_counts": np.zeros(G, np.uint32), "point_voxel": np.zeros(n, np.uint32)}
+        self._check(self._lib.gdf_seg_download_voxel_table(
+            self._h, _ptr(r["vox_cells"]), _ptr(r["vox_counts"]), G, _ptr(r["point_voxel"]), n,
+            None, 0))
+        if self.voxel_table_device()["weights"]:
+            _, total = self.object_points_counts()
+            r["weights"] = np.zeros(total, np.uint32)
+            self._check(self._lib.gdf_seg_download_voxel_table(
+                self._h, None, None, 0, None, 0, _ptr(r["weights"]), total))
+        return r
+
+    def voxel_table_device(self) -> dict:
+        """Device pointers (ints; weights 0 without object_voxels' grouped result) of the table."""
+        p = [C.c_void_p() for _ in range(5)]
+        self._check(self._lib.gdf_seg_get_device_voxel_table(self._h, *[C.byref(x) for x in p]))
+        keys = ("vox_cells", "vox_counts", "point_voxel", "weights", "count")
+        return {k: (x.value or 0) for k, x in zip(keys, p)}
+
+    def voxel_table_times(self) -> np.ndarray:
+        """Milliseconds of the last profiled table call: [clear, mark, row sums + scan, expand,
+        rank] and, after object_voxels, [ids + sizes, group, weights]."""
+        n = C.c_uint32(0)
+        self._check(self._lib.gdf_seg_get_voxel_table_times(self._h, None, 0, C.byref(n)))
+        ms = np.zeros(n.value, np.float32)
+        self._check(self._lib.gdf_seg_get_voxel_table_times(self._h, _ptr(ms), n.value, C.byref(n)))
+        return ms
 
     def set_profiling(self, enable: bool):
         self._check(self._lib.gdf_seg_set_profiling(self._h, int(bool(enable))))
