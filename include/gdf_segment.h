@@ -291,6 +291,84 @@ int gdf_seg_get_device_voxel_table(gdf_segmenter* seg, const uint32_t** vox_cell
 int gdf_seg_get_voxel_table_times(gdf_segmenter* seg, float* ms, uint32_t capacity,
                                   uint32_t* count);
 
+/* ---- the object layer per segment of the rows; per frame of a batch --------------
+ *
+ * No reference counterpart; the rules are this library's specification.
+ *   segments     seg_start[nseg + 1]: u32 words on the device, 1 <= nseg <= 64, made non-decreasing
+ *                and clamped to n_cap on read, as gdf_radius_filter_segments does:
+ *                start'[s] = min(max(seg_start[0..s]), n_cap).  Row i lies in segment s iff
+ *                start'[s] <= i < start'[s + 1]; rows in no segment are neither read nor written;
+ *                empty segments are legal anywhere.
+ *   partition    a row is kept iff ids[i] < nobj and (keep == NULL or keep[ids[i]]); its group is
+ *                g = s(i) * nobj + ids[i].  The output is the kept rows stably partitioned by g:
+ *                segment-major, then object, then input order, all four words bit for bit.
+ *                grp_start[nseg * nobj + 1] ([0] = 0, the last = the kept total, a device word too)
+ *                takes obj_start's place; index[j] is the (global) input row of output row j;
+ *                seg_out_start[s] = grp_start[s * nobj], nseg + 1 words.  Segment s's part equals
+ *                gdf_seg_group_points on the rows [start'[s], start'[s + 1]) alone, with index
+ *                shifted by start'[s] and obj_start by seg_out_start[s].
+ *   table        a row with cells[i] >= C is outside and gets point_voxel[i] = GDF_VOX_NONE; else
+ *                its key is (s(i), cells[i]).  vox_cells[G]: the plain cells of the distinct keys,
+ *                segment-major and ascending inside a segment; vox_seg_start[nseg + 1]: the first
+ *                voxel of each segment, [nseg] = G (a device word too); point_voxel[i]: the global
+ *                voxel index; vox_counts[g]: the rows with point_voxel == g.  Segment s's part
+ *                equals gdf_seg_voxel_table on its rows alone, shifted by vox_seg_start[s].
+ * All integers, a stable partition: the results are exact.
+ *
+ * A segmented grouped result is THE grouped result of the segmenter and a segmented table THE
+ * table; the getters and downloads above serve them unchanged, with these sizes:
+ *   obj_start   nseg * nobj + 1 words (grp_start), so obj_capacity must be at least that;
+ *               gdf_seg_get_object_points still reports nobj (the labelling's, or the argument) and
+ *               the kept total; ids are plain object ids, voxels nobj words
+ *   moments     gdf_seg_object_moments on the result gives nseg * nobj records in group order, one
+ *               per (segment, object); gdf_seg_download_object_moments needs that capacity, and the
+ *               device getter's array has that length.  gdf_obj_shapes_from_moments is unchanged
+ *               (pass nseg * nobj as its count).
+ * Bounds: nseg * nobj <= 2^24 and nseg * C <= 2^28, else GDF_ERR_ARG.  GDF_ERR_ARG too for nseg
+ * outside 1..64, nobj == 0, C == 0 and null pointers; n_cap == 0 succeeds with empty results.  Every
+ * refusal comes before the first launch and leaves an earlier result readable.  No host wait (the
+ * stage calls: the one for nobj after a labelling); the workspace is grow-only. */
+int gdf_seg_group_points_segments(gdf_segmenter* seg, const float* points_device,
+                                  const uint32_t* ids_device, uint32_t n_cap,
+                                  const uint32_t* seg_start_device, uint32_t nseg, uint32_t nobj,
+                                  const uint8_t* keep_device);
+int gdf_seg_voxel_table_segments(gdf_segmenter* seg, const uint32_t* cells_device, uint32_t n_cap,
+                                 const uint32_t* seg_start_device, uint32_t nseg, uint32_t num_cells);
+
+/* The stage calls on an engine's batch, on the engine's stream: one segment per frame, the segments
+ * being the engine's own device ranges (the tables gdf_get_batch_ranges downloads: the frames' point
+ * ranges for the compacted points and coords, their voxel ranges for the voxelized rows); a single
+ * frame is the one segment {0, its device count}.  Ids are taken against the segmenter's current
+ * labelling, normally gdf_seg_label_engine_grid after the batch (the grid after the batch's last
+ * frame); a batch's coords hold plain cells, so the id of a row is the rule of
+ * gdf_seg_object_points on its cell, and voxels / keep are that call's.  With an occupancy lifetime
+ * below the batch's frame count, cells of earlier frames may have decayed: their points get
+ * GDF_OBJ_NONE, which is the rule and no error.
+ * gdf_seg_object_points_batch: ids[n] of all frames' points and the points partitioned by
+ * (frame, object).  gdf_seg_object_voxels_batch: the segmented table of the batch's coords; ids[G] of
+ * vox_cells; the engine's voxelized rows, min(G, the voxelize's own count) of them, partitioned by
+ * (frame of the voxel, object); weights as gdf_seg_object_voxels gives them.  On an engine's batch
+ * vox_seg_start equals the engine's voxel ranges.
+ * GDF_ERR_STATE: what gdf_seg_object_points / gdf_seg_object_voxels refuse, except the multi-frame
+ * batch; a batch without frame ranges.  GDF_ERR_ARG: nframes * nobj > 2^24, nframes * cells > 2^28.
+ * The profiled times are those of the single-frame calls (the composite pass before the table's
+ * clear is not among them). */
+int gdf_seg_object_points_batch(gdf_segmenter* seg, gdf_engine* engine, uint32_t min_voxels);
+int gdf_seg_object_voxels_batch(gdf_segmenter* seg, gdf_engine* engine, uint32_t min_voxels);
+
+/* seg_out_start of the segmented grouped result: nseg and, with seg_out_start != NULL, its nseg + 1
+ * words (waits; GDF_ERR_CAPACITY below that).  GDF_ERR_STATE when the grouped result is not a
+ * segmented one. */
+int gdf_seg_get_group_segments(gdf_segmenter* seg, uint32_t* nseg, uint32_t* seg_out_start,
+                               uint32_t capacity);
+int gdf_seg_get_device_group_segments(gdf_segmenter* seg, const uint32_t** seg_out_start_device,
+                                      uint32_t* nseg);
+/* vox_seg_start of the segmented table, in the same way */
+int gdf_seg_get_voxel_segments(gdf_segmenter* seg, uint32_t* nseg, uint32_t* vox_seg_start,
+                               uint32_t capacity);
+int gdf_seg_get_device_voxel_segments(gdf_segmenter* seg, const uint32_t** vox_seg_start_device,
+                                      uint32_t* nseg);
+
 #ifdef __cplusplus
 }
 #endif

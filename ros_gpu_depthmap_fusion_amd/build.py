@@ -12,9 +12,10 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB_PATH = os.path.join(PKG, "lib", "libgdf.so")
 SOURCES = ["gdf_kernels.hip", "gdf_segment.hip", "gdf_filter.hip", "gdf_object_points.hip",
-           "gdf_object_moments.hip", "gdf_voxel_table.hip", "gdf_scan.hip", "gdf_engine.cpp", "gdf_driver.cpp", "gdf_fused.cpp"]
+           "gdf_object_moments.hip", "gdf_voxel_table.hip", "gdf_object_segments.hip", "gdf_scan.hip", "gdf_engine.cpp", "gdf_driver.cpp", "gdf_fused.cpp"]
 HEADERS = ["gdf_device.hpp", "gdf_kernels.hpp", "gdf_voxsum.hpp", "gdf_trace.hpp", "gdf_filter.hpp",
-           "gdf_object_points.hpp", "gdf_object_moments.hpp", "gdf_voxel_table.hpp", "gdf_scan.hpp"]
+           "gdf_object_points.hpp", "gdf_object_moments.hpp", "gdf_voxel_table.hpp", "gdf_object_segments.hpp",
+           "gdf_scan.hpp"]
 
 # Float contract of SURVEY.md Appendix A: no FMA contraction, correctly rounded / and sqrt.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",

@@ -30,6 +30,7 @@
 #include "gdf_kernels.hpp"
 #include "gdf_filter.hpp"
 #include "gdf_object_points.hpp"
+#include "gdf_object_segments.hpp"
 #include "gdf_voxel_table.hpp"
 
 using namespace gdf;
@@ -2324,6 +2325,46 @@ int gdf::engine_frame_voxels(gdf_engine* e, FrameVoxels* out) {
         Slot& q = e->sl();
         if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "object voxels before the frame's voxelize");
         out->vox = q.d_vox.as<float4>();
+        out->n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
+        out->cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, 0xFFFFFFFFu);
+    });
+}
+
+// The addressed slot's batch for gdf_seg_object_points_batch / gdf_seg_object_voxels_batch: all
+// frames' compacted points and coords with the frames' point ranges (nullptr for one frame, whose
+// count is the kCount word).  engine_frame_points' refusals but the batch one.
+int gdf::engine_batch_points(gdf_engine* e, BatchPoints* out) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (!q.frame_pts || !q.compacted) fail(GDF_ERR_STATE, "object points before the frame's compaction");
+        if (q.frame_parts)
+            fail(GDF_ERR_STATE, "object points: not for a frame armed with the emit partition");
+        if (!e->grid_set || !q.coords_valid) fail(GDF_ERR_STATE, "object points need the frame's voxel coords");
+        const bool batch = q.nframes > 1;
+        if (batch && !q.d_fstart.p) fail(GDF_ERR_STATE, "object points: the batch has no frame ranges");
+        out->pts = q.d_pts.as<float4>();
+        out->coords = q.d_coords.as<uint32_t>();
+        out->fstart = batch ? q.d_fstart.as<uint32_t>() : nullptr;
+        out->n_dev = q.d_misc.as<uint32_t>() + kCount;
+        out->cap = q.n_total;
+        out->nframes = std::max<uint32_t>(q.nframes, 1u);
+        std::memcpy(out->gs, e->gs, 12);
+        out->stream = e->s();
+        out->device = e->device;
+    });
+}
+
+// ... and its voxelized rows with the frames' voxel ranges
+int gdf::engine_batch_voxels(gdf_engine* e, BatchVoxels* out) {
+    ENGINE_OR_FAIL(e);
+    return guarded(e, [&] {
+        Slot& q = e->sl();
+        if (!q.frame_vox || !q.vox_valid) fail(GDF_ERR_STATE, "object voxels before the frame's voxelize");
+        const bool batch = q.nframes > 1;
+        if (batch && !q.d_fvox.p) fail(GDF_ERR_STATE, "object voxels: the batch has no frame ranges");
+        out->vox = q.d_vox.as<float4>();
+        out->fvox = batch ? q.d_fvox.as<uint32_t>() : nullptr;
         out->n_dev = q.d_misc.as<uint32_t>() + kVoxCount;
         out->cap = (uint32_t)std::min<size_t>(q.d_vox.bytes / 16, 0xFFFFFFFFu);
     });

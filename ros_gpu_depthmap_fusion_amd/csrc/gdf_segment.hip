@@ -38,6 +38,7 @@
 #include "gdf_kernels.hpp"
 #include "gdf_object_moments.hpp"
 #include "gdf_object_points.hpp"
+#include "gdf_object_segments.hpp"
 #include "gdf_voxel_table.hpp"
 
 namespace {
@@ -897,6 +898,12 @@ struct gdf_segmenter {
         bool valid = false, have_ids = false;  // have_ids: ids and voxels belong to the result
         bool n_on_device = false;              // words[1] holds n (else n == n_cap)
         uint32_t nobj = 0, n_cap = 0;
+        // a segmented result (gdf_object_segments.hip): nseg > 0, the groups are
+        // (segment, object) pairs and obj_start / the moments hold ngroups = nseg * nobj of them;
+        // segs: the call's clamped starts, seg_out: seg_out_start.  An unsegmented one: nseg == 0,
+        // ngroups == nobj.
+        GpuBuf keys, segs, seg_out;
+        uint32_t nseg = 0, ngroups = 0;
         hipStream_t stream = nullptr;          // the stream of the last call
         bool profiling = false;
         std::vector<hipEvent_t> ev;
@@ -911,6 +918,10 @@ struct gdf_segmenter {
     // words: {G, n}.
     struct VoxelTable {
         GpuBuf bitmap, row_rank, sums, word_rank, words, vox_cells, vox_counts, point_voxel, weights;
+        // a segmented table: nseg > 0; comp: the composite cells, segs: the call's
+        // clamped starts, seg_start: vox_seg_start
+        GpuBuf comp, segs, seg_start;
+        uint32_t nseg = 0;
         bool valid = false;
         bool n_on_device = false;   // words[1] holds n (else n == n_cap)
         bool have_weights = false;  // weights belong to the standing grouped result (object voxels)
@@ -1419,7 +1430,8 @@ void group_points(gdf_segmenter* g, const float4* pts, const uint32_t* ids, uint
     SEGCHK(w.out.ensure(nb * 16));
     SEGCHK(w.index.ensure(nb * 4));
     SEGCHK(w.obj_start.ensure(((size_t)nobj + 1) * 4));
-    w.nobj = nobj;
+    w.nobj = w.ngroups = nobj;
+    w.nseg = 0;
     w.n_cap = n_cap;
     w.stream = s;
     w.n_on_device = n_cap != 0 && n_dev != nullptr;
@@ -1529,9 +1541,12 @@ hipEvent_t* vt_events(gdf_segmenter* g) {
 // the table of (cells, n) into the segmenter's buffers, on s
 // (a voxel has a row and a cell of its own, so G <= min(n_cap, C): the per-voxel arrays hold that
 // many words).  limit_dev != nullptr: words[2] = min(G, *limit_dev), else G.
+// first_dev != nullptr: the rows below *first_dev are skipped (a segmented table).
 void voxel_table(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap, const uint32_t* n_dev,
-                 uint32_t C, const uint32_t* limit_dev, hipStream_t s, hipEvent_t* ev) {
+                 uint32_t C, const uint32_t* limit_dev, hipStream_t s, hipEvent_t* ev,
+                 const uint32_t* first_dev = nullptr) {
     gdf_segmenter::VoxelTable& t = g->vt;
+    t.nseg = 0;
     const size_t nb = std::max(n_cap, 1u);
     const uint32_t vox_cap = std::min(n_cap, C);
     SEGCHK(t.words.ensure(256));
@@ -1555,6 +1570,7 @@ void voxel_table(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap, const 
     gdf::VoxTableArgs a{};
     a.cells = cells;
     a.n_dev = n_dev;
+    a.first_dev = first_dev;
     a.n_cap = n_cap;
     a.num_cells = C;
     a.bitmap = t.bitmap.as<uint32_t>();
@@ -1582,6 +1598,97 @@ void vt_counts(gdf_segmenter* g, uint32_t* G, uint32_t* n) {
     SEGCHK(hipStreamSynchronize(t.stream));
     *n = t.n_on_device ? std::min(h[1], t.n_cap) : t.n_cap;
     *G = std::min(h[0], *n);
+}
+
+
+// ---- the object layer per segment --------------------------------------------------
+void check_nseg(uint32_t nseg) {
+    if (nseg == 0 || nseg > gdf::kOsMaxSegs) seg_fail(GDF_ERR_ARG, "segments: 1..64 segments");
+}
+
+void check_groups(uint32_t nseg, uint32_t nobj) {
+    check_nobj(nobj);
+    if ((uint64_t)nseg * nobj > gdf::kOpMaxObjects)
+        seg_fail(GDF_ERR_ARG, "segments: more than 2^24 (segment, object) groups");
+}
+
+void check_segment_cells(uint32_t nseg, uint64_t C) {
+    if (C == 0) seg_fail(GDF_ERR_ARG, "voxel table: no cells");
+    if ((uint64_t)nseg * C > gdf::kVtMaxCells)
+        seg_fail(GDF_ERR_ARG, "voxel table: more than 2^28 (segment, cell) pairs");
+}
+
+// the clamped starts of a call into buf (65 words at most); seg_start == nullptr: {0, n}
+void segment_starts(GpuBuf& buf, const uint32_t* seg_start, const uint32_t* n_dev, uint32_t nseg,
+                    uint32_t n_cap, hipStream_t s) {
+    SEGCHK(buf.ensure((gdf::kOsMaxSegs + 1) * 4));
+    SEGCHK(gdf::launch_segment_starts(gdf::SegStartArgs{seg_start, n_dev, nseg, n_cap, buf.as<uint32_t>()}, s));
+}
+
+// the segmented partition of (pts, ids) into the segmenter's result buffers; op.segs holds the call's
+// clamped starts (segment_starts).  The groups are the keys s * nobj + id through §12's passes.
+void group_points_segments(gdf_segmenter* g, const float4* pts, const uint32_t* ids, uint32_t n_cap,
+                           uint32_t nseg, uint32_t nobj, const uint8_t* keep, hipStream_t s,
+                           hipEvent_t* ev) {
+    gdf_segmenter::ObjectPoints& w = g->op;
+    const uint32_t groups = nseg * nobj;
+    SEGCHK(w.keys.ensure((size_t)std::max(n_cap, 1u) * 4));
+    SEGCHK(w.seg_out.ensure((gdf::kOsMaxSegs + 1) * 4));
+    const uint32_t* starts = w.segs.as<const uint32_t>();
+    SEGCHK(gdf::launch_segment_keys(
+        gdf::SegKeyArgs{ids, starts, nseg, n_cap, nobj, keep, w.keys.as<uint32_t>()}, s));
+    group_points(g, pts, w.keys.as<const uint32_t>(), n_cap, starts + nseg, groups, nullptr, s, ev);
+    SEGCHK(gdf::launch_segment_group_starts(w.obj_start.as<const uint32_t>(), nseg, nobj,
+                                            w.seg_out.as<uint32_t>(), s));
+    w.nobj = nobj;
+    w.nseg = nseg;
+}
+
+// the segmented table of (cells, starts) into the segmenter's buffers: vt.segs holds the call's
+// clamped starts.  §14's passes on the composite cells, then the plain cells and vox_seg_start.
+void voxel_table_segments(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap, uint32_t nseg,
+                          uint32_t C, const uint32_t* limit_dev, hipStream_t s, hipEvent_t* ev) {
+    gdf_segmenter::VoxelTable& t = g->vt;
+    SEGCHK(t.comp.ensure((size_t)std::max(n_cap, 1u) * 4));
+    SEGCHK(t.seg_start.ensure((gdf::kOsMaxSegs + 1) * 4));
+    const uint32_t* starts = t.segs.as<const uint32_t>();
+    SEGCHK(gdf::launch_segment_cells(gdf::SegCellArgs{cells, starts, nseg, n_cap, C, t.comp.as<uint32_t>()}, s));
+    voxel_table(g, t.comp.as<const uint32_t>(), n_cap, starts + nseg, nseg * C, limit_dev, s, ev, starts);
+    if (n_cap == 0) {
+        SEGCHK(hipMemsetAsync(t.seg_start.p, 0, ((size_t)nseg + 1) * 4, s));
+    } else {
+        gdf::SegTableFinishArgs f{};
+        f.bitmap = t.bitmap.as<const uint32_t>();
+        f.word_rank = t.word_rank.as<const uint32_t>();
+        f.G = t.words.as<const uint32_t>();
+        f.nseg = nseg;
+        f.C = C;
+        f.vox_cap = std::min(n_cap, nseg * C);
+        f.vox_cells = t.vox_cells.as<uint32_t>();
+        f.vox_seg_start = t.seg_start.as<uint32_t>();
+        SEGCHK(gdf::launch_segment_table_finish(f, s));
+    }
+    t.nseg = nseg;
+}
+
+// nseg + 1 words of a segment table to the host (waits), clamped to the call's capacity
+void download_segments(const GpuBuf& buf, uint32_t nseg, uint32_t clamp, hipStream_t s, uint32_t* out) {
+    SEGCHK(hipMemcpyAsync(out, buf.p, ((size_t)nseg + 1) * 4, hipMemcpyDeviceToHost, s));
+    SEGCHK(hipStreamSynchronize(s));
+    for (uint32_t k = 0; k <= nseg; ++k) out[k] = std::min(out[k], clamp);
+}
+
+// what both batch stage calls refuse on the engine's side, and the batch itself
+gdf::BatchPoints batch_points_or_fail(gdf_segmenter* g, gdf_engine* e, const char* what) {
+    need_connections(g);
+    gdf::BatchPoints bp{};
+    const int rc = gdf::engine_batch_points(e, &bp);
+    if (rc != GDF_OK) seg_fail(rc, gdf_last_error());
+    if (bp.gs[0] != g->W || bp.gs[1] != g->H || bp.gs[2] != g->L)
+        seg_fail(GDF_ERR_STATE, std::string(what) + ": the labelled grid is not the engine's grid");
+    if (bp.device != g->device) seg_fail(GDF_ERR_STATE, std::string(what) + ": the engine is on another device");
+    check_nseg(bp.nframes);
+    return bp;
 }
 
 }  // namespace
@@ -1804,14 +1911,14 @@ int gdf_seg_download_object_points(gdf_segmenter* g, uint32_t* ids, uint32_t ids
             seg_fail(GDF_ERR_STATE, "object points: gdf_seg_group_points computes no ids and no voxels");
         if (ids && ids_cap < n) seg_fail(GDF_ERR_CAPACITY, "ids capacity too small");
         if ((pts || index) && pts_cap < t) seg_fail(GDF_ERR_CAPACITY, "points capacity too small");
-        if (obj_start && obj_cap < w.nobj + 1) seg_fail(GDF_ERR_CAPACITY, "obj_start capacity too small");
+        if (obj_start && obj_cap < w.ngroups + 1) seg_fail(GDF_ERR_CAPACITY, "obj_start capacity too small");
         if (voxels && obj_cap < w.nobj) seg_fail(GDF_ERR_CAPACITY, "voxels capacity too small");
         const hipStream_t s = w.stream;
         if (ids && n) SEGCHK(hipMemcpyAsync(ids, w.ids.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         if (pts && t) SEGCHK(hipMemcpyAsync(pts, w.out.p, (size_t)t * 16, hipMemcpyDeviceToHost, s));
         if (index && t) SEGCHK(hipMemcpyAsync(index, w.index.p, (size_t)t * 4, hipMemcpyDeviceToHost, s));
         if (obj_start)
-            SEGCHK(hipMemcpyAsync(obj_start, w.obj_start.p, ((size_t)w.nobj + 1) * 4, hipMemcpyDeviceToHost, s));
+            SEGCHK(hipMemcpyAsync(obj_start, w.obj_start.p, ((size_t)w.ngroups + 1) * 4, hipMemcpyDeviceToHost, s));
         if (voxels) SEGCHK(hipMemcpyAsync(voxels, w.voxels.p, (size_t)w.nobj * 4, hipMemcpyDeviceToHost, s));
         SEGCHK(hipStreamSynchronize(s));
     });
@@ -1855,14 +1962,14 @@ int gdf_seg_object_moments(gdf_segmenter* g, const float lower[3], const float c
         const hipStream_t s = w.stream;
         StreamUse use(g, s);
         w.om_valid = false;
-        SEGCHK(w.moments.ensure((size_t)w.nobj * sizeof(gdf_obj_moments)));
+        SEGCHK(w.moments.ensure((size_t)w.ngroups * sizeof(gdf_obj_moments)));
         SEGCHK(w.om_partial.ensure(gdf::om_partial_records(w.n_cap) * sizeof(gdf_obj_moments)));
         gdf::ObjMomentArgs a{};
         a.pts = w.out.as<const float4>();
         a.obj_start = w.obj_start.as<const uint32_t>();
         a.total = w.words.as<const uint32_t>();
         a.n_cap = w.n_cap;
-        a.nobj = w.nobj;
+        a.nobj = w.ngroups;  // (a segmented result: one record per (segment, object))
         for (int k = 0; k < 3; ++k) {
             a.lower[k] = lower[k];
             a.cell[k] = cell[k];
@@ -1881,9 +1988,9 @@ int gdf_seg_download_object_moments(gdf_segmenter* g, gdf_obj_moments* out, uint
         gdf_segmenter::ObjectPoints& w = g->op;
         if (!out) seg_fail(GDF_ERR_ARG, "object moments: null argument");
         if (!w.valid || !w.om_valid) seg_fail(GDF_ERR_STATE, "no object moments (call gdf_seg_object_moments)");
-        if (cap < w.nobj) seg_fail(GDF_ERR_CAPACITY, "object moments capacity too small");
+        if (cap < w.ngroups) seg_fail(GDF_ERR_CAPACITY, "object moments capacity too small");
         SEGCHK(hipSetDevice(g->device));
-        SEGCHK(hipMemcpyAsync(out, w.moments.p, (size_t)w.nobj * sizeof(gdf_obj_moments),
+        SEGCHK(hipMemcpyAsync(out, w.moments.p, (size_t)w.ngroups * sizeof(gdf_obj_moments),
                               hipMemcpyDeviceToHost, w.stream));
         SEGCHK(hipStreamSynchronize(w.stream));
     });
@@ -2025,6 +2132,179 @@ int gdf_seg_get_device_voxel_table(gdf_segmenter* g, const uint32_t** vox_cells,
     if (point_voxel) *point_voxel = t.point_voxel.as<const uint32_t>();
     if (weights) *weights = t.have_weights && g->op.valid ? t.weights.as<const uint32_t>() : nullptr;
     if (count) *count = t.words.as<const uint32_t>();
+    return GDF_OK;
+}
+
+// ---- the object layer per segment; per frame of an engine's batch ------------------
+int gdf_seg_group_points_segments(gdf_segmenter* g, const float* pts, const uint32_t* ids, uint32_t n_cap,
+                                  const uint32_t* seg_start, uint32_t nseg, uint32_t nobj,
+                                  const uint8_t* keep) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        if (!pts || !ids || !seg_start) seg_fail(GDF_ERR_ARG, "group points: null argument");
+        check_nseg(nseg);
+        check_groups(nseg, nobj);
+        SEGCHK(hipSetDevice(g->device));
+        g->op.valid = g->op.om_valid = false;
+        g->op.have_ids = false;
+        g->vt.have_weights = false;  // (they belong to the grouped result this call replaces)
+        const hipStream_t s = g->s();
+        StreamUse use(g, s);
+        hipEvent_t* ev = op_events(g, nseg * nobj, s);
+        segment_starts(g->op.segs, seg_start, nullptr, nseg, n_cap, s);
+        group_points_segments(g, reinterpret_cast<const float4*>(pts), ids, n_cap, nseg, nobj, keep, s, ev);
+    });
+}
+
+int gdf_seg_voxel_table_segments(gdf_segmenter* g, const uint32_t* cells, uint32_t n_cap,
+                                 const uint32_t* seg_start, uint32_t nseg, uint32_t C) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        if (!cells || !seg_start) seg_fail(GDF_ERR_ARG, "voxel table: null argument");
+        check_nseg(nseg);
+        check_segment_cells(nseg, C);
+        SEGCHK(hipSetDevice(g->device));
+        g->vt.valid = g->vt.have_weights = false;
+        const hipStream_t s = g->s();
+        StreamUse use(g, s);
+        segment_starts(g->vt.segs, seg_start, nullptr, nseg, n_cap, s);
+        voxel_table_segments(g, cells, n_cap, nseg, C, nullptr, s, vt_events(g));
+    });
+}
+
+int gdf_seg_object_points_batch(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) {
+    if (!g || !e) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        // every refusal comes before the first launch
+        const gdf::BatchPoints bp = batch_points_or_fail(g, e, "object points");
+        const uint32_t nseg = bp.nframes;
+        SEGCHK(hipSetDevice(g->device));
+        const hipStream_t s = bp.stream;
+        StreamUse use(g, s);
+        ensure_merged(g, s);  // (the one wait: nobj sizes the object tables)
+        const uint32_t nobj = g->nobj;
+        check_groups(nseg, nobj);
+        gdf_segmenter::ObjectPoints& w = g->op;
+        w.valid = w.om_valid = false;
+        w.have_ids = false;
+        g->vt.have_weights = false;
+        SEGCHK(w.ids.ensure((size_t)std::max(bp.cap, 1u) * 4));
+        SEGCHK(w.voxels.ensure((size_t)nobj * 4));
+        SEGCHK(w.keep.ensure(nobj));
+        hipEvent_t* ev = op_events(g, nseg * nobj, s);
+        // one segment per frame: the engine's own point ranges (one frame: {0, its device count})
+        segment_starts(w.segs, bp.fstart, bp.n_dev, nseg, bp.cap, s);
+        object_ids_and_sizes(g, bp.coords, bp.cap, w.segs.as<const uint32_t>() + nseg, nobj, min_voxels, s);
+        group_points_segments(g, bp.pts, w.ids.as<const uint32_t>(), bp.cap, nseg, nobj,
+                              w.keep.as<const uint8_t>(), s, ev);
+        w.have_ids = true;
+    });
+}
+
+int gdf_seg_object_voxels_batch(gdf_segmenter* g, gdf_engine* e, uint32_t min_voxels) {
+    if (!g || !e) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        // every refusal comes before the first launch
+        const gdf::BatchPoints bp = batch_points_or_fail(g, e, "object voxels");
+        gdf::BatchVoxels bv{};
+        const int rc = gdf::engine_batch_voxels(e, &bv);
+        if (rc != GDF_OK) seg_fail(rc, gdf_last_error());
+        const uint32_t nseg = bp.nframes;
+        const uint64_t C = (uint64_t)g->W * g->H * g->L;
+        check_segment_cells(nseg, C);
+        SEGCHK(hipSetDevice(g->device));
+        const hipStream_t s = bp.stream;
+        StreamUse use(g, s);
+        ensure_merged(g, s);  // (the one wait: nobj sizes the object tables)
+        const uint32_t nobj = g->nobj;
+        check_groups(nseg, nobj);
+        gdf_segmenter::ObjectPoints& w = g->op;
+        gdf_segmenter::VoxelTable& t = g->vt;
+        w.valid = w.om_valid = false;
+        w.have_ids = false;
+        w.nev = 0;
+        t.valid = t.have_weights = false;
+        // a voxel has a row and a (segment, cell) pair; the grouped rows are the engine's voxelized
+        // rows, min(G, the voxelize's own count) of them, as in gdf_seg_object_voxels
+        const uint32_t gcap = std::min(bp.cap, (uint32_t)(nseg * C));
+        const uint32_t vcap = std::min(gcap, bv.cap);
+        SEGCHK(w.ids.ensure((size_t)std::max(gcap, 1u) * 4));
+        SEGCHK(w.voxels.ensure((size_t)nobj * 4));
+        SEGCHK(w.keep.ensure(nobj));
+        SEGCHK(t.weights.ensure((size_t)std::max(vcap, 1u) * 4));
+        hipEvent_t* ev = vt_events(g);
+        // 1. the table of the batch's coords, one segment per frame
+        segment_starts(t.segs, bp.fstart, bp.n_dev, nseg, bp.cap, s);
+        voxel_table_segments(g, bp.coords, bp.cap, nseg, (uint32_t)C, bv.n_dev, s, ev);
+        if (bp.cap == 0) ev = nullptr;  // (no passes, no times)
+        // 2. the ids of the voxels' plain cells
+        const uint32_t* G = t.words.as<const uint32_t>();
+        object_ids_and_sizes(g, t.vox_cells.as<const uint32_t>(), gcap, G, nobj, min_voxels, s);
+        if (ev) SEGCHK(hipEventRecord(ev[gdf::kVtEvents], s));
+        // 3. and 4. voxel g lies in the segment vox_seg_start gives it: the voxelized rows partitioned
+        segment_starts(w.segs, t.seg_start.as<const uint32_t>(), G + 2, nseg, vcap, s);
+        group_points_segments(g, bv.vox, w.ids.as<const uint32_t>(), vcap, nseg, nobj,
+                              w.keep.as<const uint8_t>(), s, nullptr);
+        w.have_ids = true;
+        if (ev) SEGCHK(hipEventRecord(ev[gdf::kVtEvents + 1], s));
+        // 5. the weights
+        SEGCHK(gdf::launch_voxel_weights(t.vox_counts.as<const uint32_t>(), w.index.as<const uint32_t>(),
+                                         w.words.as<const uint32_t>(), vcap, t.weights.as<uint32_t>(), s));
+        if (ev) {
+            SEGCHK(hipEventRecord(ev[gdf::kVtEvents + 2], s));
+            t.nev = gdf::kVtEvents + kVtExtraEvents;
+        }
+        t.have_weights = true;
+    });
+}
+
+int gdf_seg_get_group_segments(gdf_segmenter* g, uint32_t* nseg, uint32_t* seg_out_start, uint32_t cap) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        const gdf_segmenter::ObjectPoints& w = g->op;
+        if (!w.valid || w.nseg == 0) seg_fail(GDF_ERR_STATE, "no segmented grouped result");
+        if (nseg) *nseg = w.nseg;
+        if (!seg_out_start) return;
+        if (cap < w.nseg + 1) seg_fail(GDF_ERR_CAPACITY, "group segments: need nseg + 1 entries");
+        SEGCHK(hipSetDevice(g->device));
+        download_segments(w.seg_out, w.nseg, w.n_cap, w.stream, seg_out_start);
+    });
+}
+
+int gdf_seg_get_device_group_segments(gdf_segmenter* g, const uint32_t** seg_out_start, uint32_t* nseg) {
+    if (!g) return GDF_ERR_ARG;
+    const gdf_segmenter::ObjectPoints& w = g->op;
+    if (!w.valid || w.nseg == 0) {
+        gdf::set_last_error("no segmented grouped result");
+        return GDF_ERR_STATE;
+    }
+    if (seg_out_start) *seg_out_start = w.seg_out.as<const uint32_t>();
+    if (nseg) *nseg = w.nseg;
+    return GDF_OK;
+}
+
+int gdf_seg_get_voxel_segments(gdf_segmenter* g, uint32_t* nseg, uint32_t* vox_seg_start, uint32_t cap) {
+    if (!g) return GDF_ERR_ARG;
+    return seg_guarded([&] {
+        const gdf_segmenter::VoxelTable& t = g->vt;
+        if (!t.valid || t.nseg == 0) seg_fail(GDF_ERR_STATE, "no segmented voxel table");
+        if (nseg) *nseg = t.nseg;
+        if (!vox_seg_start) return;
+        if (cap < t.nseg + 1) seg_fail(GDF_ERR_CAPACITY, "voxel segments: need nseg + 1 entries");
+        SEGCHK(hipSetDevice(g->device));
+        download_segments(t.seg_start, t.nseg, t.n_cap, t.stream, vox_seg_start);
+    });
+}
+
+int gdf_seg_get_device_voxel_segments(gdf_segmenter* g, const uint32_t** vox_seg_start, uint32_t* nseg) {
+    if (!g) return GDF_ERR_ARG;
+    const gdf_segmenter::VoxelTable& t = g->vt;
+    if (!t.valid || t.nseg == 0) {
+        gdf::set_last_error("no segmented voxel table");
+        return GDF_ERR_STATE;
+    }
+    if (vox_seg_start) *vox_seg_start = t.seg_start.as<const uint32_t>();
+    if (nseg) *nseg = t.nseg;
     return GDF_OK;
 }
 

@@ -31,9 +31,12 @@ __device__ __forceinline__ uint32_t vt_n(const uint32_t* n_dev, uint32_t n_cap) 
     return n_dev ? min(*n_dev, n_cap) : n_cap;
 }
 
-// the cell of row i; kVtNone for a row at or beyond n and for a cell outside the grid
+// the first row of the call (a segmented table skips the rows before its first segment)
+__device__ __forceinline__ uint32_t vt_first(const VoxTableArgs& a) { return a.first_dev ? *a.first_dev : 0u; }
+
+// the cell of row i; kVtNone for a row outside [first, n) and for a cell outside the grid
 __device__ __forceinline__ uint32_t vt_cell(const VoxTableArgs& a, uint32_t n, uint64_t i) {
-    if (i >= n) return kVtNone;
+    if (i >= n || i < vt_first(a)) return kVtNone;
     const uint32_t c = a.cells[i];
     return c < a.num_cells ? c : kVtNone;
 }
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(kT) void k_vt_rank(const VoxTableArgs a) {
     const uint32_t c = vt_cell(a, n, i);
     uint32_t g = kVtNone;
     if (c != kVtNone) g = a.word_rank[c >> 5] + (uint32_t)__popc(a.bitmap[c >> 5] & ((1u << (c & 31u)) - 1u));
-    if (i < n) a.point_voxel[i] = g;
+    if (i < n && i >= vt_first(a)) a.point_voxel[i] = g;
     // runs of equal cells inside the wave: the head adds the run's length (an outside row or one
     // beyond n differs from every cell, so it ends a run; its own run adds nothing)
     const uint32_t below = __shfl_up(c, 1, 64);

@@ -27,6 +27,7 @@ inline size_t vt_scan_words(uint32_t num_cells) { return scan_words(vt_rows(num_
 struct VoxTableArgs {
     const uint32_t* cells;
     const uint32_t* n_dev;
+    const uint32_t* first_dev;  // nullptr, or a device word: rows below it are neither read nor written
     uint32_t n_cap, num_cells;
     uint32_t* bitmap;        // [vt_words(num_cells)]
     uint32_t* row_rank;      // [vt_rows(num_cells) + 1]: row sums, then their exclusive scan

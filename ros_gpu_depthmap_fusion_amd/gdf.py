@@ -184,6 +184,11 @@ EXPORTED = [
     "gdf_seg_voxel_table", "gdf_seg_object_voxels", "gdf_seg_get_voxel_table",
     "gdf_seg_download_voxel_table", "gdf_seg_get_device_voxel_table",
     "gdf_seg_get_voxel_table_times",
+    # ... the object layer per segment of the rows; per frame of a batch
+    "gdf_seg_group_points_segments", "gdf_seg_voxel_table_segments", "gdf_seg_object_points_batch",
+    "gdf_seg_object_voxels_batch", "gdf_seg_get_group_segments",
+    "gdf_seg_get_device_group_segments", "gdf_seg_get_voxel_segments",
+    "gdf_seg_get_device_voxel_segments",
     # include/gdf_filter.h: the radius outlier filter
     "gdf_radius_filter_plan", "gdf_radius_filter_points", "gdf_radius_filter",
     "gdf_set_radius_filter", "gdf_get_filtered_count", "gdf_download_filtered_points",
@@ -341,6 +346,14 @@ def load_library(path: str = LIB_PATH):
         "gdf_seg_download_voxel_table": (i32, [vp, vp, vp, u32, vp, u32, vp, u32]),
         "gdf_seg_get_device_voxel_table": (i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp)]),
         "gdf_seg_get_voxel_table_times": (i32, [vp, vp, u32, P(u32)]),
+        "gdf_seg_group_points_segments": (i32, [vp, vp, vp, u32, vp, u32, u32, vp]),
+        "gdf_seg_voxel_table_segments": (i32, [vp, vp, u32, vp, u32, u32]),
+        "gdf_seg_object_points_batch": (i32, [vp, vp, u32]),
+        "gdf_seg_object_voxels_batch": (i32, [vp, vp, u32]),
+        "gdf_seg_get_group_segments": (i32, [vp, P(u32), vp, u32]),
+        "gdf_seg_get_device_group_segments": (i32, [vp, P(vp), P(u32)]),
+        "gdf_seg_get_voxel_segments": (i32, [vp, P(u32), vp, u32]),
+        "gdf_seg_get_device_voxel_segments": (i32, [vp, P(vp), P(u32)]),
         "gdf_obj_shapes_from_moments": (i32, [vp, u32, vp, vp, vp]),
         "gdf_radius_filter_plan": (i32, [P(RadiusFilterParams), vp, vp]),
         "gdf_radius_filter_points": (i32, [vp, vp, u32, P(RadiusFilterParams), vp, vp, vp]),
@@ -1268,14 +1281,17 @@ class Segmenter:
 
     def object_points_results(self) -> dict:
         """points [total, 4], index [total], obj_start [nobj + 1], nobj, total and - after
-        object_points - ids [the point count of that call's frame] and voxels [nobj]."""
+        object_points - ids [the point count of that call's frame] and voxels [nobj].  A segmented
+        result (group_points_segments, the batch calls): obj_start [nseg * nobj + 1], to be sliced
+        with group_segments()."""
         nobj, total = self.object_points_counts()
+        groups = self._group_count(nobj)
         r = {"nobj": nobj, "total": total,
              "points": np.zeros((total, 4), np.float32), "index": np.zeros(total, np.uint32),
-             "obj_start": np.zeros(nobj + 1, np.uint32)}
+             "obj_start": np.zeros(groups + 1, np.uint32)}
         self._check(self._lib.gdf_seg_download_object_points(
             self._h, None, 0, _ptr(r["points"]), _ptr(r["index"]), total, _ptr(r["obj_start"]),
-            None, nobj + 1))
+            None, groups + 1))
         if self.object_points_device()["ids"]:
             n = C.c_uint32(0)
             self._check(self._lib.gdf_seg_get_object_points_input(self._h, C.byref(n)))
@@ -1304,8 +1320,9 @@ class Segmenter:
 
     def object_moments_results(self) -> np.ndarray:
         nobj, _ = self.object_points_counts()
-        out = np.zeros(nobj, OBJ_MOMENTS_DTYPE)
-        self._check(self._lib.gdf_seg_download_object_moments(self._h, _ptr(out), nobj))
+        groups = self._group_count(nobj)  # (a segmented result: one record per (segment, object))
+        out = np.zeros(groups, OBJ_MOMENTS_DTYPE)
+        self._check(self._lib.gdf_seg_download_object_moments(self._h, _ptr(out), groups))
         return out
 
     def object_moments_device(self) -> int:
@@ -1365,6 +1382,69 @@ class Segmenter:
         ms = np.zeros(n.value, np.float32)
         self._check(self._lib.gdf_seg_get_voxel_table_times(self._h, _ptr(ms), n.value, C.byref(n)))
         return ms
+
+    # ---- the object layer per segment of the rows; per frame of a batch ------------------------
+    def _group_count(self, nobj: int) -> int:
+        """Groups of the standing grouped result: nseg * nobj for a segmented one, else nobj."""
+        p, n = C.c_void_p(), C.c_uint32(0)
+        if self._lib.gdf_seg_get_device_group_segments(self._h, C.byref(p), C.byref(n)) != 0:
+            return nobj
+        return n.value * nobj
+
+    def group_points_segments(self, points_ptr: int, ids_ptr: int, n_cap: int, seg_start_ptr: int,
+                              nseg: int, nobj: int, keep_ptr: int = 0):
+        """The stable partition of device float4 points by (segment, id): seg_start_ptr addresses
+        nseg + 1 device u32 starts; read the result with object_points_results() (obj_start holds
+        nseg * nobj + 1 words) and group_segments()."""
+        self._check(self._lib.gdf_seg_group_points_segments(
+            self._h, C.c_void_p(points_ptr), C.c_void_p(ids_ptr), n_cap,
+            C.c_void_p(seg_start_ptr or None), nseg, nobj, C.c_void_p(keep_ptr or None)))
+
+    def voxel_table_segments(self, cells_ptr: int, n_cap: int, seg_start_ptr: int, nseg: int,
+                             num_cells: int):
+        """The voxel table of a device u32 array of cell indices per segment of its rows; read it
+        with voxel_table_results() and voxel_segments()."""
+        self._check(self._lib.gdf_seg_voxel_table_segments(
+            self._h, C.c_void_p(cells_ptr), n_cap, C.c_void_p(seg_start_ptr or None), nseg,
+            num_cells))
+
+    def object_points_batch(self, engine: "GPUDepthmapFusion", min_voxels: int = 0):
+        """object_points for every frame of the engine's batch, one segment per frame, on the
+        engine's stream (after label_engine_grid with SEG_CONNECTIONS)."""
+        self._check(self._lib.gdf_seg_object_points_batch(self._h, engine._h, min_voxels))
+
+    def object_voxels_batch(self, engine: "GPUDepthmapFusion", min_voxels: int = 0):
+        """object_voxels for every frame of the engine's batch, one segment per frame, on the
+        engine's stream."""
+        self._check(self._lib.gdf_seg_object_voxels_batch(self._h, engine._h, min_voxels))
+
+    def _segments(self, get) -> np.ndarray:
+        n = C.c_uint32(0)
+        self._check(get(self._h, C.byref(n), None, 0))
+        out = np.zeros(n.value + 1, np.uint32)
+        self._check(get(self._h, C.byref(n), _ptr(out), n.value + 1))
+        return out
+
+    def group_segments(self) -> np.ndarray:
+        """seg_out_start [nseg + 1] of the segmented grouped result (waits)."""
+        return self._segments(self._lib.gdf_seg_get_group_segments)
+
+    def voxel_segments(self) -> np.ndarray:
+        """vox_seg_start [nseg + 1] of the segmented table (waits)."""
+        return self._segments(self._lib.gdf_seg_get_voxel_segments)
+
+    def _segments_device(self, get):
+        p, n = C.c_void_p(), C.c_uint32(0)
+        self._check(get(self._h, C.byref(p), C.byref(n)))
+        return (p.value or 0), n.value
+
+    def group_segments_device(self):
+        """(device pointer of seg_out_start, nseg) of the segmented grouped result."""
+        return self._segments_device(self._lib.gdf_seg_get_device_group_segments)
+
+    def voxel_segments_device(self):
+        """(device pointer of vox_seg_start, nseg) of the segmented table."""
+        return self._segments_device(self._lib.gdf_seg_get_device_voxel_segments)
 
     def set_profiling(self, enable: bool):
         self._check(self._lib.gdf_seg_set_profiling(self._h, int(bool(enable))))
